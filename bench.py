@@ -7,7 +7,8 @@ synthetic crops that already live in HBM.  Workload at N=1 = BASELINE.json confi
 `[64,1024]`, 256x256 crops, batch 32, fp32 (reference: train.py:184-194 + train_script.py defaults; ReLU/BatchNorm/
 Adam-amsgrad = the reference's Adam configuration, train.py:174,380-385).
 Prints ONE JSON line on rank 0 with `roofline` (dominant MFMA kernel, HIP-event timed inside the timed region) and
-`cpu_baseline` (the CPU oracle = port of the reference's torch path, bounded sample, N=1 only).
+`cpu_baseline` (the CPU oracle = port of the reference's torch path, bounded sample, N=1 only); the blocks after the
+headline in brief (see brief()), so that the line stays well below 8 KB.
 """
 import argparse
 import json
@@ -50,11 +51,10 @@ def parse():
                          "for small batches / bf16, where the host cannot enqueue ~600 launches per step fast enough")
     ap.add_argument("--no-inference", action="store_true", help="skip the secondary inference (Mpixels/s) measurement")
     ap.add_argument("--train-only", action="store_true",
-                    help="(internal) the training blocks (+ cpu_baseline) only: the default single-GPU run measures them in a "
-                         "child process of their own")
+                    help="the training blocks (+ cpu_baseline) only, no inference child process (profiling tools)")
     ap.add_argument("--inference-only", action="store_true",
                     help="(internal) run only the inference block and print {\"inference\": ...}: the default run measures it in "
-                         "a child process of its own, started before the parent touches the GPU")
+                         "a child process of its own, started after the training blocks")
     ap.add_argument("--infer-size", type=int, default=2048)
     ap.add_argument("--infer-frames", type=int, default=16, help="T of the 2D+t stack (SURVEY.md §8d: T = 16)")
     ap.add_argument("--no-bf16-block", action="store_true",
@@ -63,6 +63,10 @@ def parse():
     ap.add_argument("--rehearse", action="store_true",
                     help="CPU rehearsal of the multi-rank contract (gloo, no kernels): launcher, rendezvous, barrier + "
                          "max-over-ranks timing and the JSON line, with a sleep as the step; `value` is meaningless")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step of the headline block computed to DIR/<name>.npy (rank 0): "
+                         "its loss and predictions, a fixed seeded sample of the updated parameters / running statistics "
+                         "and of the parameter gradients; float32 / float64, at most 64 MB in all")
     return ap.parse_args()
 
 
@@ -87,12 +91,14 @@ def launch_ranks(args):
 
 
 def inference_child(args):
-    """The inference block in a process of its own, run to completion BEFORE this process touches the GPU (a child of a
-    process without a HIP context, like launch_ranks).  Blocks that share one process disturb each other through the
-    allocator: the 2048^2 frames of the inference block and the batch-32 tensors of the training blocks leave each other an
-    address space cut into pieces, and whichever block ran second measured 4 % (bf16 training step, 40.63 vs 39.02 ms) to
-    9 % (bf16 product-path inference, 258 vs 283 Mpx/s) slower than on its own — same box, same kernels.  Returns the
-    block's dict, or None when the child failed (the caller then measures in-process)."""
+    """The inference block in a fresh process of its own, started after this process has measured the training blocks
+    (FIRST, on a chip that has not just run 30 s of inference: the fp32 matrix kernels hold 2.33-2.37 GHz on a cool chip and
+    the headline step measured 131.1-131.7 ms at the start of a process tree, 133.8-135.0 ms right behind the inference
+    block) and released their memory.  Blocks that share one process disturb each other through the allocator: the 2048^2
+    frames of the inference block and the batch-32 tensors of the training blocks leave each other an address space cut into
+    pieces, and whichever block ran second measured 4 % (bf16 training step, 40.63 vs 39.02 ms) to 9 % (bf16 product-path
+    inference, 258 vs 283 Mpx/s) slower than on its own — same box, same kernels.  Returns the block's dict, or None when
+    the child failed (the caller then measures in-process)."""
     import subprocess
     cmd = [sys.executable, os.path.abspath(__file__), "--inference-only", "--arch", args.arch, "--act", args.act,
            "--norm", args.norm, "--filters", str(args.filters[0]), str(args.filters[1]),
@@ -107,32 +113,6 @@ def inference_child(args):
     return None
 
 
-def run_in_children(args):
-    """Default single-GPU run: the training blocks and the inference block each in a fresh process, the training blocks
-    FIRST — on a chip that has not just run 30 s of inference (the fp32 matrix kernels hold 2.33-2.37 GHz on a cool chip
-    and the headline step measured 131.1-131.7 ms at the start of a process tree, 133.8-135.0 ms right behind the inference
-    block) — and neither disturbed by the other's allocations.  This process never touches the GPU.  Returns the merged
-    dict, or None when the training child failed (the caller then runs everything in-process)."""
-    import subprocess
-    cmd = [sys.executable, os.path.abspath(__file__), "--train-only"] + [a for a in sys.argv[1:] if a != "--train-only"]
-    out = None
-    try:
-        r = subprocess.run(cmd, stdout=subprocess.PIPE, text=True, timeout=3000)
-        for line in reversed(r.stdout.splitlines()):
-            if line.startswith("{"):
-                out = json.loads(line)
-                break
-    except Exception:
-        out = None
-    if out is None:
-        return None
-    if not args.no_inference and args.arch == "DU":
-        inf = inference_child(args)
-        if inf is not None:
-            out["inference"] = inf
-    return out
-
-
 def synthetic_batch(batch, size, arch, seed, device):
     """Synthetic crops of the training tensor contract (training_dataset.py:30-63 + mytransforms.py:380-406):
     img fp32 in [-1,1] (1,H,W); distance labels fp32 in [0,1]; boundary labels int64 in {0,1,2}."""
@@ -145,6 +125,39 @@ def synthetic_batch(batch, size, arch, seed, device):
         l1 = torch.randint(0, 3, (batch, size, size), generator=g)
         l2 = None
     return tuple(t.to(device) if t is not None else None for t in (img, l1, l2))
+
+
+DUMP_SAMPLE = 1 << 21          # elements per sampled array of --dump-outputs (8 MB as float32)
+
+
+def _dump_sample(t, n=DUMP_SAMPLE, seed=0):
+    """t flattened to float32 on the host: whole when it has at most n elements, else n elements at seeded random
+    (sorted) positions — the same positions in every run of the same workload"""
+    import numpy as np
+    flat = t.detach().reshape(-1)
+    if flat.numel() > n:
+        idx = np.sort(np.random.default_rng(seed).choice(flat.numel(), n, replace=False))
+        flat = flat[torch.from_numpy(idx).to(flat.device)]
+    return flat.float().cpu().numpy()
+
+
+def dump_outputs(path, net, loss, preds):
+    """--dump-outputs: what the last timed training step computed, as a caller of the step sees it afterwards — the loss,
+    the network's predictions, the updated parameters and running statistics, the parameter gradients.  The last two are
+    large (~46 M values for the [64,1024] DU-Net): a fixed seeded sample of each.  <= 4 x 8 MB + the loss."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    model = getattr(net, "module", net)
+    names = ("border", "cell") if len(preds) == 2 else ("prediction",)
+    arrays = {"loss": np.array(float(loss.item()), dtype=np.float64)}
+    for name, p in zip(names, preds):
+        arrays[name] = _dump_sample(p, seed=1)
+    state = [v.reshape(-1) for v in model.state_dict().values() if v.is_floating_point()]
+    arrays["state_sample"] = _dump_sample(torch.cat([v.float() for v in state]), seed=2)
+    grads = [(p.grad if p.grad is not None else torch.zeros_like(p)).reshape(-1) for p in model.parameters()]
+    arrays["grad_sample"] = _dump_sample(torch.cat([g.float() for g in grads]), seed=3)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def host_cores():
@@ -554,8 +567,9 @@ def rehearse(args, world, rank):
               flush=True)
 
 
-def train_metric(args, dev, world, rank, timing=True):
-    """W untimed + K timed training steps of the workload `args` names; returns (JSON dict, net)."""
+def train_metric(args, dev, world, rank, timing=True, dump_dir=None):
+    """W untimed + K timed training steps of the workload `args` names; returns (JSON dict, net).  dump_dir: where
+    rank 0 writes what the K-th timed step computed (dump_outputs)."""
     import torch.distributed as dist
     from microbeseg_amd import engine
     from microbeseg_amd.utils.unets import build_unet
@@ -578,16 +592,21 @@ def train_metric(args, dev, world, rank, timing=True):
     crit = get_loss("smooth_l1", "distance") if args.arch == "DU" else get_loss("ce_dice", "boundary")
     batches = [synthetic_batch(args.batch, args.size, args.arch, 1234 + 17 * rank + i, dev) for i in range(2)]
     net.train()
+    dump = dump_dir is not None and rank == 0
+    last = {}        # --dump-outputs: the latest step's loss and predictions (a recorded graph's static tensors)
 
     def one_step(img, l1, l2):
         opt.zero_grad()
         if args.arch == "DU":
-            border, cell = net(img)
+            border, cell = preds = net(img)
             loss = crit["border"](border, l1) + crit["cell"](cell, l2)
         else:
-            loss = crit(net(img), l1)
+            preds = (net(img),)
+            loss = crit(preds[0], l1)
         loss.backward()
         opt.step()
+        if dump:         # (detached: the step's autograd graph must not outlive it)
+            last["loss"], last["preds"] = loss.detach(), [p.detach() for p in preds]
         return loss
 
     warmup = args.warmup
@@ -625,6 +644,9 @@ def train_metric(args, dev, world, rank, timing=True):
     # hipMalloc / hipFree calls of the caching allocator inside the timed region (each one synchronises the device: a
     # steady-state step makes none)
     alloc_calls = {k: int(ms1.get(k, 0) - ms0.get(k, 0)) for k in ("num_device_alloc", "num_device_free", "num_alloc_retries")}
+    if dump:
+        dump_outputs(dump_dir, net, last["loss"], last["preds"])
+        last.clear()
     engine.set_kernel_timer(None)
     dt_bracketed = None
     if two_pass:
@@ -712,13 +734,21 @@ def train_metric(args, dev, world, rank, timing=True):
                                                      "total_ms_per_step": round(f["total_ms"] / args.steps, 3),
                                                      "launches_per_step": f["launches"] // args.steps}
                                       for f in sorted(fams.values(), key=lambda f: -f["total_ms"])}
-            out["kernels"] = {k: {"tflops": round(v["tflops"], 2), "total_ms_per_step": round(v["total_ms"] / args.steps, 3),
-                                  "avg_launch_ms": round(v["avg_ms"], 4), "launches_per_step": v["launches"] // args.steps}
-                              for k, v in kernels.items()}
     del opt, batches
     for p_ in net.parameters():
         p_.grad = None
     return out, net
+
+
+def brief(blk):
+    """A block after the headline as the JSON line carries it: rate, step time, dominant kernel family.  The line must
+    stay well below 8 KB, or a reader that keeps the last 8 KB of the output gets no whole line (with every block in full
+    it was ~21 KB); per-kernel times of any configuration come from a profile (tools/prof_bench.sh)."""
+    out = {k: blk[k] for k in ("value", "ms_per_step", "steps", "host_enqueue_ms_per_step", "frac_of_fp32_mfma_peak",
+                               "frac_of_bf16_mfma_peak", "graph_replay") if k in blk}
+    if "roofline" in blk:
+        out["roofline"] = {k: blk["roofline"][k] for k in ("kernel", "achieved", "frac")}
+    return out
 
 
 def release(*objs):
@@ -744,13 +774,7 @@ def main():
         raise SystemExit(f"bench.py: --gpus {args.gpus} but the launcher started {world} rank(s)")
     if args.rehearse:
         return rehearse(args, world, rank)
-    if world == 1 and not in_rank_env and not args.train_only and not args.inference_only:
-        merged = run_in_children(args)
-        if merged is not None:
-            print(json.dumps(merged), flush=True)
-            return
     want_inference = rank == 0 and world == 1 and not args.no_inference and args.arch == "DU" and not args.train_only
-    inference = inference_child(args) if (want_inference and not args.inference_only) else None
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs an MI355X (no CPU fallback)")
     # one rank per GPU.  MSEG_BENCH_BACKEND=gloo is a single-GPU rehearsal of the N-rank path (ranks share the visible
@@ -778,7 +802,7 @@ def main():
         net_i = build_unet(args.arch, args.act, "conv", args.norm, dev, 1, ch_out=1, filters=tuple(args.filters))
         print(json.dumps({"inference": inference_metric(args, net_i, dev)}), flush=True)
         return
-    out, net = train_metric(args, dev, world, rank, timing=not args.no_kernel_timing)
+    out, net = train_metric(args, dev, world, rank, timing=not args.no_kernel_timing, dump_dir=args.dump_outputs)
     headline = workload_key(args) == {"batch": 32, "size": 256, "arch": "DU", "act": "relu", "norm": "bn",
                                       "filters": [64, 1024], "optimizer": "adam", "precision": "fp32"}
     del net
@@ -793,7 +817,7 @@ def main():
         del net2
         release()
         engine.set_precision(args.precision)
-        out["bf16_320"] = blk
+        out["bf16_320"] = brief(blk)
         # further configurations of the path, each a short run with its own roofline: the boundary method's
         # U-Net with ce_dice, GroupNorm (the north-star's norm), the GUI / CLI default batch of 4
         out["secondary"] = {}
@@ -809,7 +833,6 @@ def main():
             blk, net3 = train_metric(a3, dev, 1, 0, timing=not args.no_kernel_timing)
             del net3
             release()
-            blk.pop("kernels", None)                     # the per-instantiation table stays with the two main blocks
             if a3.batch == 4:
                 # batch 4 (the GUI / CLI default), ~600 launches per step: the same step replayed from a hipGraph
                 # (training/graph_step.py, TrainWorker.graph_steps) — what the recording buys is host time
@@ -819,23 +842,23 @@ def main():
                 del net4
                 release()
                 blk["graph_replay"] = {k: rep[k] for k in ("value", "ms_per_step", "host_enqueue_ms_per_step")}
-            out["secondary"][tag] = blk
+            out["secondary"][tag] = brief(blk)
         engine.set_precision(args.precision)
-    # (the inference block was measured first, in a child process of its own: inference_child)
-    if inference is not None:
-        out["inference"] = inference
-    elif want_inference:
-        # (in-process fallback)
-        # a freshly initialised network (fixed seed): the few optimisation steps above on random labels leave a network whose
-        # outputs are nearly constant, i.e. frames without seeds and a watershed with nothing to do
-        from microbeseg_amd.utils.unets import build_unet
-        torch.manual_seed(3)
-        net_i = build_unet(args.arch, args.act, "conv", args.norm, dev, 1, ch_out=1, filters=tuple(args.filters))
-        out["inference"] = inference_metric(args, net_i, dev)
-        del net_i
     release()
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args, tuple(args.filters))
+    if want_inference:
+        # after the training blocks (they run first, on a cool chip) and in a child process of its own: inference_child
+        out["inference"] = inference_child(args)
+        if out["inference"] is None:
+            # (in-process fallback)
+            # a freshly initialised network (fixed seed): the few optimisation steps above on random labels leave a network
+            # whose outputs are nearly constant, i.e. frames without seeds and a watershed with nothing to do
+            from microbeseg_amd.utils.unets import build_unet
+            torch.manual_seed(3)
+            net_i = build_unet(args.arch, args.act, "conv", args.norm, dev, 1, ch_out=1, filters=tuple(args.filters))
+            out["inference"] = inference_metric(args, net_i, dev)
+            del net_i
     if world > 1:
         dist.destroy_process_group()
     if rank == 0:

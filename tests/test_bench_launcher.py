@@ -1,11 +1,13 @@
 """CPU: `python bench.py --gpus 2` starts two ranks itself (torch.distributed.run, 127.0.0.1 rendezvous) and rank 0
 prints ONE JSON line with n_gpus == 2 — the launcher / barrier / max-over-ranks path of the driver contract, rehearsed
-with gloo and no kernels (`--rehearse`)."""
+with gloo and no kernels (`--rehearse`); and what `--dump-outputs` writes."""
 import json
 import os
 import pathlib
 import subprocess
 import sys
+
+import pytest
 
 ROOT = pathlib.Path(__file__).resolve().parents[1]
 
@@ -63,3 +65,55 @@ def test_pmc_profile_is_selected_by_workload_and_kernel_sources(monkeypatch):
         break
     a.size = 512                               # no profile of that workload: say so instead of borrowing another one's
     assert bench.pmc_traffic("igemm_halo_bf16w4_kernel<0, true>", a) == {"traffic": None, "traffic_source": "none"}
+
+
+def test_dump_outputs_writes_seeded_samples(tmp_path):
+    """--dump-outputs: float32 / float64 arrays, the large ones cut to the same seeded sample in every run, 64 MB at most"""
+    import numpy as np
+    import torch
+    sys.path.insert(0, str(ROOT))
+    import bench
+    torch.manual_seed(0)
+    net = torch.nn.Sequential(torch.nn.Conv2d(1, 4, 3), torch.nn.BatchNorm2d(4))
+    preds = [torch.rand(3 << 20), torch.rand(2, 1, 8, 8)]   # one prediction above the sample size, one below
+    loss = net(torch.rand(2, 1, 8, 8)).square().mean()
+    loss.backward()
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), net, loss.detach(), preds)
+    got = {p.stem: np.load(p) for p in (tmp_path / "a").iterdir()}
+    assert set(got) == {"loss", "border", "cell", "state_sample", "grad_sample"}
+    assert got["loss"].dtype == np.float64 and got["loss"] == np.float64(loss.item())
+    assert all(a.dtype == np.float32 for k, a in got.items() if k != "loss")
+    assert got["border"].shape == (bench.DUMP_SAMPLE,) and np.isin(got["border"], preds[0].numpy()).all()
+    assert np.array_equal(got["cell"], preds[1].numpy().ravel())
+    n_state = sum(v.numel() for v in net.state_dict().values() if v.is_floating_point())
+    assert got["state_sample"].shape == (n_state,) and got["grad_sample"].shape == (sum(p.numel() for p in net.parameters()),)
+    assert np.array_equal(got["grad_sample"], torch.cat([p.grad.ravel() for p in net.parameters()]).numpy())
+    for k, a in got.items():
+        assert np.array_equal(a, np.load(tmp_path / "b" / f"{k}.npy"))
+
+
+@pytest.mark.gpu
+def test_dump_outputs_come_from_the_last_timed_step(tmp_path):
+    """Same arguments -> the same outputs; one more timed step (--steps) -> a later step's outputs"""
+    import numpy as np
+    import torch
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    small = ["--batch", "2", "--size", "64", "--filters", "16", "64", "--warmup", "1", "--no-cpu-baseline",
+             "--no-inference", "--no-kernel-timing"]
+    dumps = {}
+    for tag, steps in (("a", 2), ("b", 2), ("c", 3)):
+        r = _run(["--gpus", "1", "--steps", str(steps), "--dump-outputs", str(tmp_path / tag)] + small)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1 and json.loads(lines[0])["steps"] == steps
+        dumps[tag] = {p.stem: np.load(p) for p in (tmp_path / tag).iterdir()}
+    a, b, c = dumps["a"], dumps["b"], dumps["c"]
+    assert set(a) == {"loss", "border", "cell", "state_sample", "grad_sample"}
+    assert a["border"].shape == a["cell"].shape == (2 * 64 * 64,)
+    assert all(np.isfinite(v).all() for v in a.values())
+    np.testing.assert_allclose(b["loss"], a["loss"], rtol=1e-5)
+    for k in ("border", "cell"):
+        np.testing.assert_allclose(b[k], a[k], rtol=1e-4, atol=1e-5)
+    assert abs(float(c["loss"]) - float(a["loss"])) > 1e-4 * abs(float(a["loss"]))
