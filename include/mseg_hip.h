@@ -182,6 +182,7 @@ int mseg_first_conv_fwd(const float* x4, const float* w, const float* bias, int 
  *                            first layer does not take the kernel above                                                   */
 #define MSEG_PIX_U8 0
 #define MSEG_PIX_U16 1
+#define MSEG_PIX_I32 2 /* mseg_stack_relabel only */
 int mseg_frame_minmax(const void* raw, int dtype, size_t npix, uint32_t* minmax, void* stream);
 int mseg_first_conv_fwd_raw(const void* raw, int dtype, int H0, int W0, int pad_top, int pad_left, const uint32_t* minmax,
                             const float* w, const float* bias, int Cout, void* z, int z_dtype, void* stream);
@@ -467,6 +468,41 @@ int mseg_eval_relabel(const uint16_t* mask, int H, int W, int border_width, int3
                       void* ws, size_t ws_bytes, void* stream);
 int mseg_eval_pair_counts(const int32_t* true_lab, const int32_t* pred_lab, int H, int W, int nt, int np,
                           int32_t* area_t, int32_t* area_p, int32_t* inter, void* stream);
+
+/* ---- analysis / result export (AnalysisWorker.analyze_data src/inference/analysis.py:112-170,
+ * ResultExportWorker.export_data src/inference/result_export.py:112-190) --------------------------------------------------
+ * Polygons of a whole stack in the reference's iteration order, as CSR arrays: polygon k (0-based) owns the (row, col)
+ * int32 pairs rc[2*voff[k]] .. rc[2*voff[k+1]-1], already clamped to the image as make_coordinates clamps them
+ * (analysis.py:214-234), and lies in frame frame[k] (frames outside 0..T-1 are skipped).
+ * mseg_roi_fill: mask[T][H][W] int32 = the value the reference's stack holds after `mask[t, rr, cc] = cell_id` for every
+ *   polygon (skimage.draw.polygon, analysis.py:126-128): the last polygon covering a pixel wins (atomicMax of k + 1), and
+ *   cell ids 65536 .. 66534 wrap to k & 0xFFFF as in the reference's uint16 stack (int32 from cell_id 66535 on,
+ *   analysis.py:136-137).  Zeroes mask itself.
+ * mseg_roi_outline: outlines[T][H][W] uint8 0/1 = polygon_perimeter(r, c, shape, clip=True) (analysis.py:130-132):
+ *   skimage.draw.line along every edge of the closed polygon, in-image pixels only.  Zeroes outlines itself.
+ * mseg_stack_relabel: per frame skimage.measure.label(frame, background=0) (analysis.py:139-140) of a uint16
+ *   (MSEG_PIX_U16) or int32 (MSEG_PIX_I32) stack: lab_out int32, k_out_dev[t] = components of frame t.  T*H*W < 2^31.
+ * mseg_region_stats: per frame t and label l in 1..K_t (K_t = label_off[t+1] - label_off[t], label_off on the device,
+ *   label_off[T] = n_labels) the regionprops area / axis_major_length / axis_minor_length (analysis.py:158-164) at index
+ *   label_off[t] + l - 1 (area 0: label absent), and total_area[t] = the sum of all label values of frame t (np.sum of the
+ *   mask, analysis.py:156).  Integer moment sums with 64-bit atomics (deterministic).
+ * mseg_overlay_rgb: out = uint8(clip(255 * f32(img) / max(img), 0, 255)) with outline pixels (255, 255, 0)
+ *   (result_export.py:183-190); img uint8 / uint16 [T][H][W] (C == 1; out [T][H][W][3]) or [T][H][W][C] with C >= 3
+ *   (out [T][H][W][C], channels 0..2 of outline pixels replaced).  The maximum is taken over the stack on the device.    */
+size_t mseg_roi_fill_workspace_bytes(int n_poly);
+int mseg_roi_fill(const int32_t* rc, const int64_t* voff, const int32_t* frame, int n_poly, int T, int H, int W,
+                  int32_t* mask, void* ws, size_t ws_bytes, void* stream);
+int mseg_roi_outline(const int32_t* rc, const int64_t* voff, const int32_t* frame, int n_poly, int64_t n_vert, int T, int H,
+                     int W, uint8_t* outlines, void* stream);
+size_t mseg_stack_relabel_workspace_bytes(int T, int H, int W);
+int mseg_stack_relabel(const void* values, int dtype, int T, int H, int W, int32_t* lab_out, int32_t* k_out_dev, void* ws,
+                       size_t ws_bytes, void* stream);
+size_t mseg_region_stats_workspace_bytes(int64_t n_labels);
+int mseg_region_stats(const int32_t* labels, int T, int H, int W, const int64_t* label_off, int64_t n_labels, int64_t* area,
+                      double* major, double* minor, uint64_t* total_area, void* ws, size_t ws_bytes, void* stream);
+size_t mseg_overlay_workspace_bytes(void);
+int mseg_overlay_rgb(const void* img, int dtype, int T, int H, int W, int C, const uint8_t* outlines, uint8_t* out,
+                     void* ws, size_t ws_bytes, void* stream);
 
 /* ---- misc ---------------------------------------------------------------------------------------------------- */
 int mseg_version(void);

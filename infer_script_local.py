@@ -3,7 +3,8 @@
 
 Same flags and output as the reference ``infer_script_local.py`` (:17-25, :164-165): ``--img_dir/-i``, ``--model/-m``,
 ``--thresholds/-t`` (th_cell th_seed, default 0.10 0.45), ``--result_path/-r``, ``--channel/-c``, ``--device/-d``,
-``--overwrite/-o``; writes ``mask_<stem>_channel<c>.tif`` (uint16, [T, H, W] squeezed).
+``--overwrite/-o``; writes ``mask_<stem>_channel<c>.tif`` (uint16, [T, H, W] squeezed); ``--export`` adds the files of
+the GUI's Export button (inference/result_export.py) for the segmented channel of uint8 / uint16 stacks.
 """
 import argparse
 from pathlib import Path
@@ -49,6 +50,12 @@ def main():
     parser.add_argument('--rois', default=False, action='store_true',
                         help='[extension] also write <mask file stem>_rois.json: one polygon ROI per cell and frame, the '
                              'records the OMERO route of infer_script.py uploads (traced on the device)')
+    parser.add_argument('--export', default=False, action='store_true',
+                        help='[extension] also export each stack like the GUI\'s Export button: <image stem>.tif, _mask.tif, '
+                             '_overlay.tif, _outlines.tif and _analysis.csv from the device-traced ROIs into '
+                             '<result_path>/<image stem>_channel<c>_export/.  The exported image and overlay hold the '
+                             'segmented channel only (the GUI exports every channel); uint8 / uint16 images only, other '
+                             'stacks are segmented but not exported')
     args = parser.parse_args()
 
     imgs_path = Path(args.img_dir)
@@ -80,14 +87,22 @@ def main():
         if out_file.is_file() and not args.overwrite:
             print(f'Skip {img_id.stem} (already processed and overwriting not enabled)')
             continue
+        export = args.export
+        if export and frames.dtype not in (np.uint8, np.uint16):
+            print(f'Skip export of {img_id.stem} (the overlay needs uint8 / uint16 images, got {frames.dtype})')
+            export = False
         print(f'Process {img_id.stem} (channel: {args.channel})')
         results = worker.infer_stack(frames)
         tiff.imwrite(str(out_file), np.squeeze(results))
+        if args.rois or export:
+            rois = [roi for t in range(len(results)) for roi in worker.polygon_rois(results[t], t)]
         if args.rois:
             import json
-            rois = [roi for t in range(len(results)) for roi in worker.polygon_rois(results[t], t)]
             with open(out_file.with_name(out_file.stem + '_rois.json'), 'w', encoding='utf-8') as f:
                 json.dump({'image': img_id.name, 'channel': args.channel, 'rois': rois}, f)
+        if export:
+            from microbeseg_amd.inference.result_export import export_local
+            export_local(frames, rois, result_path / f"{img_id.stem}_channel{args.channel}_export", img_id.name)
     print('--- Finished ---')
 
 

@@ -150,6 +150,15 @@ SIGNATURES = {
     "mseg_eval_pair_counts": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "mseg_polygons_find": (_I, [_P, _I, _I, _P, _P, _P, _I, _P, _P]),
     "mseg_polygons_trace": (_I, [_P, _I, _I, _P, _P, _I, _P, _P]),
+    "mseg_roi_fill_workspace_bytes": (_SZ, [_I]),
+    "mseg_roi_fill": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _SZ, _P]),
+    "mseg_roi_outline": (_I, [_P, _P, _P, _I, C.c_int64, _I, _I, _I, _P, _P]),
+    "mseg_stack_relabel_workspace_bytes": (_SZ, [_I, _I, _I]),
+    "mseg_stack_relabel": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _SZ, _P]),
+    "mseg_region_stats_workspace_bytes": (_SZ, [C.c_int64]),
+    "mseg_region_stats": (_I, [_P, _I, _I, _I, _P, C.c_int64, _P, _P, _P, _P, _P, _SZ, _P]),
+    "mseg_overlay_workspace_bytes": (_SZ, []),
+    "mseg_overlay_rgb": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _SZ, _P]),
     "mseg_version": (_I, []),
     "mseg_strerror": (C.c_char_p, [_I]),
     "mseg_last_hip_error": (_I, []),

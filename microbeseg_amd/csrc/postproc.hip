@@ -1964,3 +1964,101 @@ extern "C" int mseg_eval_pair_counts(const int32_t* true_lab, const int32_t* pre
   MSEG_LAUNCH_CHECK();
   return MSEG_OK;
 }
+
+// =====================================================================================================================
+// Stack relabel (analysis.py:139-140 / result_export.py:139-140: `for frame in range(len(mask)): mask[frame] =
+// label(mask[frame], background=0)`) — the merge / flatten / root-flag / scan pieces of mseg_eval_relabel over T frames
+// in one pass: unions never cross a frame, one exclusive scan over the whole stack ranks every frame's roots, and a
+// frame's ids start after the roots of the frames before it (its scan value at the frame's first pixel).
+struct SrWs {
+  int32_t* L; int32_t* flag; int32_t* scan; int32_t* bsum; int32_t* total;
+};
+
+static size_t sr_carve(SrWs* w, void* base, size_t n) {
+  const size_t nb = (n + SCAN_TILE - 1) / SCAN_TILE + 1;
+  size_t off = 0;
+  char* b = (char*)base;
+#define SR_TAKE(field, type, count)                         \
+  do {                                                      \
+    off = align_up(off, 256);                               \
+    if (w) w->field = (type*)(b + off);                     \
+    off += sizeof(type) * (size_t)(count);                  \
+  } while (0)
+  SR_TAKE(L, int32_t, n); SR_TAKE(flag, int32_t, n); SR_TAKE(scan, int32_t, n); SR_TAKE(bsum, int32_t, 2 * nb);
+  SR_TAKE(total, int32_t, 1);
+#undef SR_TAKE
+  return align_up(off, 256);
+}
+
+extern "C" size_t mseg_stack_relabel_workspace_bytes(int T, int H, int W) {
+  if (T <= 0 || H <= 0 || W <= 0 || (long long)T * H * W > 0x7fffffffLL) return 0;
+  return sr_carve(nullptr, nullptr, (size_t)T * H * W);
+}
+
+template <typename V>
+__global__ void sr_init_kernel(const V* __restrict__ val, size_t n, int32_t* __restrict__ L) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) L[i] = val[i] != 0 ? (int32_t)i : -1;
+}
+
+template <typename V>
+__global__ void sr_merge_kernel(const V* __restrict__ val, int32_t* __restrict__ L, int T, int H, int W) {
+  const size_t hw = (size_t)H * W, n = (size_t)T * hw;
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const V v = val[i];
+  if (v == 0) return;
+  const size_t r = i % hw;
+  const int y = (int)(r / W), x = (int)(r - (size_t)y * W);
+  if (x > 0 && val[i - 1] == v) uf_union(L, (int)i, (int)i - 1);
+  if (y > 0) {
+    if (val[i - W] == v) uf_union(L, (int)i, (int)i - W);
+    if (x > 0 && val[i - W - 1] == v) uf_union(L, (int)i, (int)i - W - 1);
+    if (x + 1 < W && val[i - W + 1] == v) uf_union(L, (int)i, (int)i - W + 1);
+  }
+}
+
+__global__ void sr_counts_kernel(const int32_t* __restrict__ scan, const int32_t* __restrict__ total, int T, size_t hw,
+                                 int32_t* __restrict__ k_out) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= T) return;
+  const int32_t end = t + 1 < T ? scan[(size_t)(t + 1) * hw] : *total;
+  k_out[t] = end - scan[(size_t)t * hw];
+}
+
+__global__ void sr_assign_kernel(const int32_t* __restrict__ L, const int32_t* __restrict__ scan, size_t n, size_t hw,
+                                 int32_t* __restrict__ out) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = L[i] >= 0 ? scan[L[i]] - scan[i - i % hw] + 1 : 0;
+}
+
+template <typename V>
+static int sr_launch(const V* val, int T, int H, int W, int32_t* lab_out, int32_t* k_out_dev, SrWs& w, hipStream_t st) {
+  const size_t hw = (size_t)H * W, n = (size_t)T * hw;
+  const unsigned nb = pp_blocks(n);
+  hipLaunchKernelGGL(sr_init_kernel<V>, dim3(nb), dim3(PP_BLOCK), 0, st, val, n, w.L);
+  hipLaunchKernelGGL(sr_merge_kernel<V>, dim3(nb), dim3(PP_BLOCK), 0, st, val, w.L, T, H, W);
+  hipLaunchKernelGGL(pp_ccl_flatten_kernel, dim3(nb), dim3(PP_BLOCK), 0, st, w.L, n);
+  hipLaunchKernelGGL(ev_rootflag_kernel, dim3(nb), dim3(PP_BLOCK), 0, st, (const int32_t*)w.L, n, w.flag);
+  MSEG_LAUNCH_CHECK();
+  if (pp_exclusive_scan(w.flag, w.scan, w.bsum, n, w.total, st)) return MSEG_ELAUNCH;
+  hipLaunchKernelGGL(sr_counts_kernel, dim3((T + PP_BLOCK - 1) / PP_BLOCK), dim3(PP_BLOCK), 0, st,
+                     (const int32_t*)w.scan, (const int32_t*)w.total, T, hw, k_out_dev);
+  hipLaunchKernelGGL(sr_assign_kernel, dim3(nb), dim3(PP_BLOCK), 0, st, (const int32_t*)w.L, (const int32_t*)w.scan, n,
+                     hw, lab_out);
+  MSEG_LAUNCH_CHECK();
+  return MSEG_OK;
+}
+
+extern "C" int mseg_stack_relabel(const void* values, int dtype, int T, int H, int W, int32_t* lab_out, int32_t* k_out_dev,
+                                  void* ws, size_t ws_bytes, void* stream) {
+  if (!values || !lab_out || !k_out_dev || !ws || (dtype != MSEG_PIX_U16 && dtype != MSEG_PIX_I32)) return MSEG_EINVAL;
+  const size_t need = mseg_stack_relabel_workspace_bytes(T, H, W);
+  if (need == 0) return MSEG_EINVAL;
+  if (ws_bytes < need) return MSEG_EWORKSPACE;
+  SrWs w;
+  sr_carve(&w, ws, (size_t)T * H * W);
+  hipStream_t st = (hipStream_t)stream;
+  return dtype == MSEG_PIX_U16 ? sr_launch((const uint16_t*)values, T, H, W, lab_out, k_out_dev, w, st)
+                               : sr_launch((const int32_t*)values, T, H, W, lab_out, k_out_dev, w, st);
+}

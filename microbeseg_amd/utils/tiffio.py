@@ -1,5 +1,7 @@
 """Minimal TIFF reader/writer for the on-disk formats of the hot path: uncompressed
-grayscale uint8 / uint16 / int32 / float32 images, single page (H, W) or multi-page stacks (T, H, W).
+grayscale uint8 / uint16 / int32 / float32 images, single page (H, W) or multi-page stacks (T, H, W), plus the export
+files of result_export.py: multi-sample stacks (T, H, W, C) (RGB for C == 3, e.g. the uint8 overlay; any C and dtype for
+the exported image) and bool stacks (1 bit per pixel).
 ``tifffile`` (what the reference uses: training_dataset.py:40, infer_script_local.py:82,165) is used when present;
 the build / GPU image does not ship it, hence this dependency-free fallback for exactly those formats."""
 import struct
@@ -55,31 +57,45 @@ def imread(path):
         fmt = t.get(339, (1,))[0]
         if comp != 1:
             raise ValueError(f"{path}: compressed TIFF (compression {comp}) needs tifffile")
-        dt = np.dtype(_DTYPES[(fmt, bits)]).newbyteorder(bo)
         offs, cnts = t[273], t[279]
         data = b"".join(buf[o:o + c] for o, c in zip(offs, cnts))
+        if bits == 1 and spp == 1:                      # bilevel: rows padded to whole bytes, most significant bit first
+            rows = np.frombuffer(data, np.uint8, count=h * ((w + 7) // 8)).reshape(h, -1)
+            pages.append(np.unpackbits(rows, axis=1)[:, :w].astype(bool))
+            continue
+        dt = np.dtype(_DTYPES[(fmt, bits)]).newbyteorder(bo)
         arr = np.frombuffer(data, dtype=dt, count=h * w * spp).astype(dt.newbyteorder("="))
         pages.append(arr.reshape((h, w, spp)) if spp > 1 else arr.reshape((h, w)))
     return pages[0] if len(pages) == 1 else np.stack(pages)
 
 
 def imwrite(path, arr):
+    """(H, W) or (T, H, W) grayscale pages, bool pages (1 bit per pixel), or (T, H, W, C) pages with C samples per pixel
+    (RGB for C == 3, RGB + alpha for C == 4, grayscale + extra samples otherwise, as tifffile writes them)."""
     arr = np.asarray(arr)
     if _tf is not None:  # pragma: no cover
         _tf.imwrite(str(path), arr)
         return
+    spp = 1
     if arr.ndim == 2:
         pages = [arr]
     elif arr.ndim == 3:
         pages = list(arr)
+    elif arr.ndim == 4 and arr.dtype != np.bool_:
+        pages, spp = list(arr), arr.shape[-1]           # contiguous samples
     else:
-        raise ValueError("only (H, W) or (T, H, W) arrays")
-    kind = {"u": 1, "i": 2, "f": 3}[arr.dtype.kind]
-    bits = arr.dtype.itemsize * 8
+        raise ValueError("only (H, W), (T, H, W) or (T, H, W, C) arrays")
+    kind = {"u": 1, "i": 2, "f": 3, "b": 1}[arr.dtype.kind]
+    bits = 1 if arr.dtype == np.bool_ else arr.dtype.itemsize * 8
+    photometric = 2 if spp in (3, 4) else 1
+    extra = spp - 3 if photometric == 2 else spp - 1   # ExtraSamples: 2 = unassociated alpha, 0 = unspecified
     out = bytearray(b"II" + struct.pack("<HI", 42, 0))
     prev_next_ptr = 4
     for p in pages:
-        p = np.ascontiguousarray(p, dtype=arr.dtype.newbyteorder("<"))
+        if bits == 1:
+            p = np.packbits(np.ascontiguousarray(p, dtype=np.uint8), axis=1)
+        else:
+            p = np.ascontiguousarray(p, dtype=arr.dtype.newbyteorder("<"))
         if len(out) % 2:
             out += b"\0"
         data_off = len(out)
@@ -88,13 +104,28 @@ def imwrite(path, arr):
             out += b"\0"
         ifd_off = len(out)
         struct.pack_into("<I", out, prev_next_ptr, ifd_off)
-        h, w = p.shape
-        entries = [(256, 4, 1, w), (257, 4, 1, h), (258, 3, 1, bits), (259, 3, 1, 1), (262, 3, 1, 1),
-                   (273, 4, 1, data_off), (277, 3, 1, 1), (278, 4, 1, h), (279, 4, 1, p.nbytes), (339, 3, 1, kind)]
-        out += struct.pack("<H", len(entries))
-        for tag, typ, cnt, val in entries:
-            out += struct.pack("<HHI", tag, typ, cnt) + (struct.pack("<HH", val, 0) if typ == 3 else struct.pack("<I", val))
+        h, w = p.shape[0], (p.shape[1] if bits != 1 else arr.shape[-1])
+        # (tag, type, values); type 3 = SHORT, 4 = LONG; values that do not fit the 4-byte entry go after the IFD
+        entries = [(256, 4, (w,)), (257, 4, (h,)), (258, 3, (bits,) * spp), (259, 3, (1,)), (262, 3, (photometric,)),
+                   (273, 4, (data_off,)), (277, 3, (spp,)), (278, 4, (h,)), (279, 4, (p.nbytes,))]
+        if spp > 1:
+            entries.append((284, 3, (1,)))             # PlanarConfiguration: contiguous
+        if extra:
+            entries.append((338, 3, (2,) if spp == 4 else (0,) * extra))
+        entries.append((339, 3, (kind,) * spp if spp > 1 else (kind,)))
+        tail_off = ifd_off + 2 + 12 * len(entries) + 4
+        ifd, tail = bytearray(struct.pack("<H", len(entries))), bytearray()
+        for tag, typ, vals in entries:
+            fmt = "H" if typ == 3 else "I"
+            raw = struct.pack("<" + fmt * len(vals), *vals)
+            ifd += struct.pack("<HHI", tag, typ, len(vals))
+            if len(raw) <= 4:
+                ifd += raw + b"\0" * (4 - len(raw))
+            else:
+                ifd += struct.pack("<I", tail_off + len(tail))
+                tail += raw + (b"\0" if len(raw) % 2 else b"")
+        out += ifd
         prev_next_ptr = len(out)
-        out += struct.pack("<I", 0)
+        out += struct.pack("<I", 0) + tail
     with open(path, "wb") as f:
         f.write(bytes(out))
