@@ -6,9 +6,12 @@ One "step" = zero_grad + forward + loss + backward (+ gradient all-reduce) + opt
 synthetic crops that already live in HBM.  Workload at N=1 = BASELINE.json configs[1]: distance-method DU-Net
 `[64,1024]`, 256x256 crops, batch 32, fp32 (reference: train.py:184-194 + train_script.py defaults; ReLU/BatchNorm/
 Adam-amsgrad = the reference's Adam configuration, train.py:174,380-385).
-Prints ONE JSON line on rank 0 with `roofline` (dominant MFMA kernel, HIP-event timed inside the timed region) and
-`cpu_baseline` (the CPU oracle = port of the reference's torch path, bounded sample, N=1 only); the blocks after the
-headline in brief (see brief()), so that the line stays well below 8 KB.
+A plain run sets up, warms up, times the K steps, writes --dump-outputs if asked, and prints ONE JSON line on rank 0: the
+headline and what follows from its own timed steps.  `--full` adds everything else the benchmark measures, each in runs of
+its own: `roofline` (dominant MFMA kernel, from a second, HIP-event bracketed pass of K steps), the bf16 320x320 and
+secondary training blocks (N=1), `cpu_baseline` (the CPU oracle = port of the reference's torch path, bounded sample, N=1
+only) and the inference block (N=1, child process); the blocks after the headline in brief (see brief()), so that the line
+stays well below 8 KB.
 """
 import argparse
 import json
@@ -44,6 +47,10 @@ def parse():
                     help="bf16 = BASELINE configs[2]: bf16 matrix-core kernels for every convolution that has one, "
                          "activations and activation gradients STORED as bf16 (DESIGN.md 4b), fp32 accumulate / weights / "
                          "normalisation statistics (the default line is the fp32 configs[1])")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything, not only the headline: the kernel table / roofline (a bracketed pass of its "
+                         "own), the bf16 320x320 and secondary blocks, the CPU baseline and the inference block; the --no-* "
+                         "options below leave parts of it out")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-timing", action="store_true", help="skip the HIP-event bracketing of MFMA kernels")
     ap.add_argument("--graph", action="store_true",
@@ -53,12 +60,12 @@ def parse():
     ap.add_argument("--train-only", action="store_true",
                     help="the training blocks (+ cpu_baseline) only, no inference child process (profiling tools)")
     ap.add_argument("--inference-only", action="store_true",
-                    help="(internal) run only the inference block and print {\"inference\": ...}: the default run measures it in "
-                         "a child process of its own, started after the training blocks")
+                    help="(internal) run only the inference block and print {\"inference\": ...}: the --full run measures it "
+                         "in a child process of its own, started after the training blocks")
     ap.add_argument("--infer-size", type=int, default=2048)
     ap.add_argument("--infer-frames", type=int, default=16, help="T of the 2D+t stack (SURVEY.md §8d: T = 16)")
     ap.add_argument("--no-bf16-block", action="store_true",
-                    help="skip the secondary BASELINE configs[2] measurement (320x320, bf16) of the default run")
+                    help="skip the secondary BASELINE configs[2] measurement (320x320, bf16) of the --full run")
     ap.add_argument("--master-port", type=int, default=0, help="rendezvous port of the self-launched ranks (0 = pick)")
     ap.add_argument("--rehearse", action="store_true",
                     help="CPU rehearsal of the multi-rank contract (gloo, no kernels): launcher, rendezvous, barrier + "
@@ -774,7 +781,8 @@ def main():
         raise SystemExit(f"bench.py: --gpus {args.gpus} but the launcher started {world} rank(s)")
     if args.rehearse:
         return rehearse(args, world, rank)
-    want_inference = rank == 0 and world == 1 and not args.no_inference and args.arch == "DU" and not args.train_only
+    want_inference = (args.full and rank == 0 and world == 1 and not args.no_inference and args.arch == "DU"
+                      and not args.train_only)
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs an MI355X (no CPU fallback)")
     # one rank per GPU.  MSEG_BENCH_BACKEND=gloo is a single-GPU rehearsal of the N-rank path (ranks share the visible
@@ -802,13 +810,15 @@ def main():
         net_i = build_unet(args.arch, args.act, "conv", args.norm, dev, 1, ch_out=1, filters=tuple(args.filters))
         print(json.dumps({"inference": inference_metric(args, net_i, dev)}), flush=True)
         return
-    out, net = train_metric(args, dev, world, rank, timing=not args.no_kernel_timing, dump_dir=args.dump_outputs)
+    # a plain run is this block alone; --full adds its bracketed kernel-timing pass and the blocks below
+    out, net = train_metric(args, dev, world, rank, timing=args.full and not args.no_kernel_timing,
+                            dump_dir=args.dump_outputs)
     headline = workload_key(args) == {"batch": 32, "size": 256, "arch": "DU", "act": "relu", "norm": "bn",
                                       "filters": [64, 1024], "optimizer": "adam", "precision": "fp32"}
     del net
     release()
-    if rank == 0 and world == 1 and headline and not args.no_bf16_block:
-        # BASELINE configs[2] next to the fp32 headline, so that the driver's default run records it too
+    if args.full and rank == 0 and world == 1 and headline and not args.no_bf16_block:
+        # BASELINE configs[2] next to the fp32 headline, so that the --full run records it too
         import copy
         a2 = copy.copy(args)
         a2.precision, a2.size, a2.graph = "bf16", 320, False
@@ -845,7 +855,7 @@ def main():
             out["secondary"][tag] = brief(blk)
         engine.set_precision(args.precision)
     release()
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args, tuple(args.filters))
     if want_inference:
         # after the training blocks (they run first, on a cool chip) and in a child process of its own: inference_child

@@ -117,3 +117,37 @@ def test_dump_outputs_come_from_the_last_timed_step(tmp_path):
     for k in ("border", "cell"):
         np.testing.assert_allclose(b[k], a[k], rtol=1e-4, atol=1e-5)
     assert abs(float(c["loss"]) - float(a["loss"])) > 1e-4 * abs(float(a["loss"]))
+
+
+def test_full_is_off_by_default(monkeypatch):
+    """A plain run (--gpus / --steps / --warmup) measures the headline alone; whatever else the benchmark measures needs
+    --full"""
+    sys.path.insert(0, str(ROOT))
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert bench.parse().full is False
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--full"])
+    assert bench.parse().full is True
+
+
+@pytest.mark.gpu
+def test_plain_run_is_the_headline_alone_and_full_adds_the_rest():
+    """A plain run prints the headline of its own timed steps and nothing that takes runs of its own; --full adds the
+    bracketed kernel-timing pass and the CPU baseline (the inference block, also --full, is left out here for time)"""
+    import torch
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    small = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "2", "--size", "64", "--filters", "16", "64"]
+    extra = ("roofline", "kernel_families", "kernel_timing", "bf16_320", "secondary", "cpu_baseline", "inference")
+    lines = {}
+    for tag, more in (("plain", []), ("full", ["--full", "--no-inference"])):
+        r = _run(small + more)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+        got = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(got) == 1, r.stdout
+        lines[tag] = json.loads(got[0])
+    for out in lines.values():
+        assert out["metric"] == "training crops/sec (64px)" and out["unit"] == "crops/s" and out["dtype"] == "f32"
+        assert out["higher_is_better"] is True and out["steps"] == 2 and out["value"] > 0 and out["ms_per_step"] > 0
+    assert not any(k in lines["plain"] for k in extra), sorted(lines["plain"])
+    assert "kernel_timing" in lines["full"] and "cpu_baseline" in lines["full"] and "inference" not in lines["full"]

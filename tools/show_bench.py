@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Pretty-print the JSON line of a bench.py log: headline + kernel-family table (sorted by time per step)."""
+"""Pretty-print the JSON line of a `bench.py --full` log: headline + kernel-family table (sorted by time per step)."""
 import json
 import sys
 
