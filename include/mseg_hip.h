@@ -188,6 +188,11 @@ int mseg_first_conv_fwd_raw(const void* raw, int dtype, int H0, int W0, int pad_
                             const float* w, const float* bias, int Cout, void* z, int z_dtype, void* stream);
 int mseg_frame_normalize(const void* raw, int dtype, int H0, int W0, int pad_top, int pad_left, const uint32_t* minmax,
                          float* out, void* stream);
+/* The same for a group of N raw frames of one size, [N][H0][W0], every frame with its own extrema: minmax [N][2], out fp32
+ * [N][H0 + pad_top][W0 + pad_left].  One launch each; every value bit-identical to the one-frame calls on that frame. */
+int mseg_frames_minmax(const void* raw, int dtype, int N, size_t npix_per_frame, uint32_t* minmax, void* stream);
+int mseg_frames_normalize(const void* raw, int dtype, int N, int H0, int W0, int pad_top, int pad_left,
+                          const uint32_t* minmax, float* out, void* stream);
 size_t mseg_first_wgrad_workspace_bytes(int N, int H, int W, int Cout);
 int mseg_first_wgrad(const float* x4, const void* dz, int dz_dtype, int N, int H, int W, int Cout, float* dW, void* ws,
                      void* stream);
@@ -390,6 +395,19 @@ int mseg_distance_postprocess_sweep(const float* border, const float* cell, int 
                                     const float* th_seed, int nth, int col_major_ids, uint16_t* labels,
                                     int32_t* n_instances_dev, int32_t* status_dev, void* ws, size_t ws_bytes,
                                     void* stream);
+
+/* Distance post-processing of N frames of one size in ONE chain of launches (a stack of small frames: the per-frame chain
+ * is ~45 launches over a few tens of thousands of pixels).  border / cell point at the un-padded origin of frame 0 inside
+ * the (possibly padded) predictions and are read in place: element (f, y, x) lies at f * frame_stride + y * row_stride + x
+ * (strides in floats).  labels [N][H][W], n_instances_dev / status_dev [N] (nullable): frame i gets, bit for bit, what
+ * mseg_distance_postprocess returns for it alone — a frame whose flood meets a tie is redone by the exact serial flood over
+ * that frame only (one workgroup per frame).  The number of launches does not depend on N.  N <= 65535,
+ * N * (H + 1) * W < 2^31; ws: mseg_postproc_batch_workspace_bytes(N, H, W) bytes.                                        */
+size_t mseg_postproc_batch_workspace_bytes(int N, int H, int W);
+int mseg_distance_postprocess_batch(const float* border, const float* cell, int N, int H, int W, long long row_stride,
+                                    long long frame_stride, float th_cell, float th_seed, int col_major_ids,
+                                    uint16_t* labels, int32_t* n_instances_dev, int32_t* status_dev, void* ws,
+                                    size_t ws_bytes, void* stream);
 
 /* ---- training augmentation on the device (src/training/mytransforms.py:12-406) ------------------
  * The reference pipeline Flip -> Contrast -> Scaling -> Rotate -> Blur -> Noise -> ToTensor runs per sample on the CPU; here

@@ -4,7 +4,8 @@
 Same flags and output as the reference ``infer_script_local.py`` (:17-25, :164-165): ``--img_dir/-i``, ``--model/-m``,
 ``--thresholds/-t`` (th_cell th_seed, default 0.10 0.45), ``--result_path/-r``, ``--channel/-c``, ``--device/-d``,
 ``--overwrite/-o``; writes ``mask_<stem>_channel<c>.tif`` (uint16, [T, H, W] squeezed); ``--export`` adds the files of
-the GUI's Export button (inference/result_export.py) for the segmented channel of uint8 / uint16 stacks.
+the GUI's Export button (inference/result_export.py) for the segmented channel of uint8 / uint16 stacks;
+``--frame_batch N`` sends the frames of a stack through the network and the post-processing in groups of N.
 """
 import argparse
 from pathlib import Path
@@ -47,6 +48,10 @@ def main():
     parser.add_argument('--sliding_window', default=False, action='store_true',
                         help='[extension] tiled inference (2048 px tiles + 128 px halo; same prediction as whole-frame '
                              'inference for the BatchNorm models training produces); lifts the 8192 px frame limit')
+    parser.add_argument('--frame_batch', default=1, type=int,
+                        help='[extension] frames of a stack that share one upload, one network forward and one batched '
+                             'post-processing call (made for stacks of small frames, 128-512 px; capped so that a group '
+                             'holds at most 2048 x 2048 pixels; same masks for fp32). 1 = frame by frame, 0 = auto')
     parser.add_argument('--rois', default=False, action='store_true',
                         help='[extension] also write <mask file stem>_rois.json: one polygon ROI per cell and frame, the '
                              'records the OMERO route of infer_script.py uploads (traced on the device)')
@@ -76,6 +81,7 @@ def main():
     worker = InferWorker(model=args.model, device=args.device, ths=args.thresholds, channel=args.channel,
                          sliding_window=args.sliding_window)
     worker.precision = args.precision
+    worker.frame_batch = args.frame_batch
     worker.text_output.connect(print)
     torch.set_grad_enabled(False)
     print('--- Start inference ---')

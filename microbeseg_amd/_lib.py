@@ -86,6 +86,8 @@ SIGNATURES = {
     "mseg_frame_minmax": (_I, [_P, _I, _SZ, _P, _P]),
     "mseg_first_conv_fwd_raw": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _I, _P]),
     "mseg_frame_normalize": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "mseg_frames_minmax": (_I, [_P, _I, _I, _SZ, _P, _P]),
+    "mseg_frames_normalize": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     "mseg_first_wgrad_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
     "mseg_first_wgrad": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "mseg_wgrad_workspace_bytes": (_SZ, [C.POINTER(MsegWgrad)]),
@@ -127,6 +129,9 @@ SIGNATURES = {
     "mseg_boundary_postprocess_post": (_I, [_I, _I, _P, _P, _P, _P, _SZ, _P]),
     "mseg_distance_postprocess_sweep": (_I, [_P, _P, _I, _I, C.POINTER(C.c_float), C.POINTER(C.c_float), _I, _I, _P, _P,
                                              _P, _P, _SZ, _P]),
+    "mseg_postproc_batch_workspace_bytes": (_SZ, [_I, _I, _I]),
+    "mseg_distance_postprocess_batch": (_I, [_P, _P, _I, _I, _I, C.c_longlong, C.c_longlong, _F, _F, _I, _P, _P, _P, _P,
+                                             _SZ, _P]),
     "mseg_aug_u16_to_f32": (_I, [_P, _P, _SZ, _P]),
     "mseg_aug_flip": (_I, [_P, _P, _I, _I, _I, _P, _P]),
     "mseg_aug_affine": (_I, [_P, _P, _I, _I, _I, _P, _P, _I, _P]),

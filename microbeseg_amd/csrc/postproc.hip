@@ -2062,3 +2062,311 @@ extern "C" int mseg_stack_relabel(const void* values, int dtype, int T, int H, i
   return dtype == MSEG_PIX_U16 ? sr_launch((const uint16_t*)values, T, H, W, lab_out, k_out_dev, w, st)
                                : sr_launch((const int32_t*)values, T, H, W, lab_out, k_out_dev, w, st);
 }
+
+// =====================================================================================================================
+// Distance post-processing of N frames of one size in ONE chain of launches (mseg_distance_postprocess_batch).
+// A stack of small frames (microfluidic chambers: 128^2 .. 512^2) spends its time between launches: the chain above is ~45
+// launches / memsets per frame over a few tens of thousands of pixels.  Here the N frames are laid out as one TALL image
+// of N * (H + 1) rows: frame f holds rows f * (H + 1) .. f * (H + 1) + H - 1, followed by one row whose mask and seeds are
+// zero.  Neither the 8-connected seed labelling nor the 4-connected flood can cross that row, so the connected-component,
+// prefix-sum, component-list and per-component flood stages run on the tall image as they are; what depends on "the frame"
+// has a frame-aware kernel below: the gaussian (reflects at frame borders, reads the prediction in place through strides),
+// the thresholds (write the tall layout), the seed statistics / totals / selection (the rule area <= max(0.1 * mean, 4) uses
+// the frame's mean: every frame has its own counter block, laid out like `counters`), the id numbering (key within the
+// frame, ids restart at 1), the taint of the flood (per frame), the exact serial redo (one workgroup per tainted frame,
+// over that frame alone: its push counter and marker order are the frame's own — a serial flood over the tall image would
+// interleave the frames' ages) and the finalize.  The number of launches does not depend on N.
+struct PPBatch {
+  int N, H, W;          // frames, un-padded frame size
+  int fpx;              // (H + 1) * W: pixels of a frame's slab of the tall image
+};
+
+static size_t ppb_carve(PPWs* w, int32_t** fcnt, void* base, int N, int H, int W) {
+  const size_t tall = pp_carve(w, base, N * (H + 1), W);
+  if (fcnt) *fcnt = (int32_t*)((char*)base + tall);
+  return align_up(tall + sizeof(int32_t) * (size_t)N * C_COUNT, 256);
+}
+
+extern "C" size_t mseg_postproc_batch_workspace_bytes(int N, int H, int W) {
+  if (N <= 0 || N > 65535 || H <= 0 || W <= 0 || (long long)N * (H + 1) * W > 0x7fffffffLL) return 0;
+  return ppb_carve(nullptr, nullptr, nullptr, N, H, W);
+}
+
+// one axis of the gaussian for every frame: in[f * fs + y * rs + x] (the prediction in place, or the tall layout),
+// out in the tall layout; same operations as pp_gauss_kernel, reflection inside the frame
+__global__ void ppb_gauss_kernel(const float* __restrict__ in, long long rs, long long fs, float* __restrict__ out,
+                                 const PPBatch b, int axis, double w0, double w1, double w2) {
+  const int il = blockIdx.x * blockDim.x + threadIdx.x;
+  if (il >= b.fpx) return;
+  const int f = blockIdx.y, H = b.H, W = b.W;
+  const int y = il / W, x = il - y * W;
+  float* o = out + (size_t)f * b.fpx + il;
+  if (y >= H) { *o = 0.f; return; }                                // the row between two frames
+  const float* fr = in + (long long)f * fs;
+  double c, m1, p1, m2, p2;
+  if (axis == 0) {
+    c = fr[(long long)y * rs + x];
+    m2 = fr[(long long)pp_reflect(y - 2, H) * rs + x]; p2 = fr[(long long)pp_reflect(y + 2, H) * rs + x];
+    m1 = fr[(long long)pp_reflect(y - 1, H) * rs + x]; p1 = fr[(long long)pp_reflect(y + 1, H) * rs + x];
+  } else {
+    const float* row = fr + (long long)y * rs;
+    c = row[x];
+    m2 = row[pp_reflect(x - 2, W)]; p2 = row[pp_reflect(x + 2, W)];
+    m1 = row[pp_reflect(x - 1, W)]; p1 = row[pp_reflect(x + 1, W)];
+  }
+  double t = __dmul_rn(c, w2);
+  t = __dadd_rn(t, __dmul_rn(__dadd_rn(m2, p2), w0));
+  t = __dadd_rn(t, __dmul_rn(__dadd_rn(m1, p1), w1));
+  *o = (float)t;
+}
+
+// pp_distance_thresh_kernel + pp_negate_kernel for every frame: mask, seeds and the flood's image (-cell) in the tall layout
+__global__ void ppb_thresh_kernel(const float* __restrict__ border, long long rs, long long fs,
+                                  const float* __restrict__ cs, const PPBatch bt, float th_cell, float th_seed,
+                                  uint8_t* __restrict__ mask, uint8_t* __restrict__ seedb, float* __restrict__ img) {
+  const int il = blockIdx.x * blockDim.x + threadIdx.x;
+  if (il >= bt.fpx) return;
+  const int f = blockIdx.y, W = bt.W;
+  const int y = il / W, x = il - y * W;
+  const size_t i = (size_t)f * bt.fpx + il;
+  if (y >= bt.H) { mask[i] = 0; seedb[i] = 0; img[i] = 0.f; return; }
+  float b = border[(long long)f * fs + (long long)y * rs + x];
+  b = b < 0.f ? 0.f : (b > 1.f ? 1.f : b);
+  const float c = cs[i];
+  mask[i] = c > th_cell;
+  const float b2 = __fmul_rn(b, b);
+  float t = (float)tan((double)b2);
+  if (t < 0.05f) t = 0.f;
+  t = t < 0.f ? 0.f : (t > 1.f ? 1.f : t);
+  seedb[i] = __fsub_rn(c, t) > th_seed;
+  img[i] = -c;
+}
+
+// pp_seed_stats_kernel per frame: workgroups do not straddle frames (blockIdx.y = frame), keys are the frame's own
+__global__ void ppb_seed_stats_kernel(const int32_t* __restrict__ L, const PPBatch b, int col_major,
+                                      int32_t* __restrict__ area, int32_t* __restrict__ ckey, int32_t* __restrict__ fcnt) {
+  const int il = blockIdx.x * blockDim.x + threadIdx.x;
+  const int f = blockIdx.y;
+  const bool in = il < b.fpx;
+  const size_t i = (size_t)f * b.fpx + il;
+  const int r = in ? L[i] : -1;
+  const int y = in ? il / b.W : 0, x = in ? il - y * b.W : 0;
+  const int run = pp_run_length(r, x);
+  if (run > 0) {
+    atomicAdd(&area[r], run);
+    atomicMin(&ckey[r], col_major ? x * b.H + y : il);
+  }
+  __shared__ int sh_cnt[2];
+  if (threadIdx.x < 2) sh_cnt[threadIdx.x] = 0;
+  __syncthreads();
+  const unsigned long long seeds = __ballot(r >= 0), roots = __ballot(r >= 0 && r == (int)i);
+  if ((threadIdx.x & 63) == 0) {
+    if (seeds) atomicAdd(&sh_cnt[0], __popcll(seeds));
+    if (roots) atomicAdd(&sh_cnt[1], __popcll(roots));
+  }
+  __syncthreads();
+  if (threadIdx.x < 2 && sh_cnt[threadIdx.x])
+    atomicAdd(&fcnt[(size_t)f * C_COUNT + C_PART + 32 * threadIdx.x + (blockIdx.x & 31)], sh_cnt[threadIdx.x]);
+}
+
+__global__ void ppb_seed_totals_kernel(int32_t* __restrict__ fcnt) {
+  int32_t* counters = fcnt + (size_t)blockIdx.x * C_COUNT;
+  const int k = threadIdx.x >> 5, j = threadIdx.x & 31;
+  int v = counters[C_PART + 32 * k + j];
+  for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  if (j == 0) counters[k == 0 ? C_TOTAL : C_NCOMP] = v;
+}
+
+__global__ void ppb_seed_select_kernel(const int32_t* __restrict__ L, size_t n, int fpx, const int32_t* __restrict__ area,
+                                       const int32_t* __restrict__ ckey, int32_t* __restrict__ flag,
+                                       int32_t* __restrict__ fcnt) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n || L[i] != (int)i) return;
+  const size_t f = i / (size_t)fpx;
+  int32_t* fc = fcnt + f * C_COUNT;
+  if (pp_keep(area[i], fc, 1)) {
+    flag[f * (size_t)fpx + ckey[i]] = 1;
+    atomicAdd(&fc[C_KEPT], 1);
+  }
+}
+
+// ids restart at 1 in every frame: rank among the kept seeds of the tall image minus the rank of the frame's first pixel
+__global__ void ppb_markers_kernel(const int32_t* __restrict__ L, size_t n, int fpx, const int32_t* __restrict__ area,
+                                   const int32_t* __restrict__ ckey, const int32_t* __restrict__ scan,
+                                   const uint8_t* __restrict__ mask, const int32_t* __restrict__ fcnt,
+                                   int32_t* __restrict__ markers, int32_t* __restrict__ out) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  int id = 0;
+  const int r = L[i];
+  if (r >= 0 && mask[i]) {
+    const size_t f = i / (size_t)fpx, fb = f * (size_t)fpx;
+    if (pp_keep(area[r], fcnt + f * C_COUNT, 1)) id = scan[fb + ckey[r]] - scan[fb] + 1;
+  }
+  markers[i] = id;
+  out[i] = id;
+}
+
+// pp_flood_wave_kernel with the taint kept per frame (a component lies inside one frame: root / fpx).  KEEP IN STEP with
+// pp_flood_wave_kernel: the body is that kernel's, line for line, except for where the taint goes and the C_SERIAL early
+// exit (the batch has no forced-serial mode); the one-frame kernel is left as it is so that its code does not change.
+template <int TILE_PX>
+__global__ __launch_bounds__(64) void ppb_flood_wave_kernel(
+    const float* __restrict__ img, const uint8_t* __restrict__ mask, const int32_t* __restrict__ mlab,
+    const int32_t* __restrict__ clist, const int32_t* __restrict__ hoff, const int32_t* __restrict__ carea,
+    const int32_t* __restrict__ bymin, const int32_t* __restrict__ bymax, const int32_t* __restrict__ bxmin,
+    const int32_t* __restrict__ bxmax, unsigned long long* __restrict__ hkey, uint32_t* __restrict__ hidx,
+    int32_t* __restrict__ hlab, int32_t* out, int H, int W, int32_t* __restrict__ counters, int32_t* __restrict__ fcnt,
+    int fpx, int work_slot, long long px_lo, long long px_hi, int tile_px, int rows_lds) {
+  __shared__ unsigned long long s_key[PPW_CAP];
+  __shared__ uint32_t s_idx[PPW_CAP];
+  __shared__ int32_t s_lab[PPW_CAP];
+  __shared__ uint32_t s_tile[TILE_PX];
+  const int lane = threadIdx.x;
+  const int ncomp = counters[C_NMCOMP];
+  for (int pass = 0; pass < 2; ++pass) {
+    for (;;) {
+      int c = 0;
+      if (lane == 0) c = atomicAdd(&counters[work_slot + pass], 1);
+      c = __builtin_amdgcn_readfirstlane(c);
+      if (c >= ncomp) break;
+      const int root = clist[c];
+      const int area = carea[root];
+      if ((area >= PPW_BIG_AREA) != (pass == 0)) continue;
+      const int y0 = bymin[root], y1 = bymax[root], x0 = bxmin[root], x1 = bxmax[root];
+      const int th = y1 - y0 + 3, tw = x1 - x0 + 3;
+      const long long px = (long long)th * tw;
+      if (px <= px_lo || px > px_hi) continue;
+      unsigned long long* gkey = hkey + hoff[root];
+      uint32_t* gidx = hidx + hoff[root];
+      int32_t* glab = hlab + hoff[root];
+      int taint;
+#define PPW_RUN(L, S) ppw_component<L, S>(s_key, s_idx, s_lab, s_tile, img, mask, mlab, gkey, gidx, glab, out, H, W, root, \
+                                          y0, x0, th, tw, rows_lds)
+      if (px > (long long)tile_px || tw > 64 * 1024 || th > 32 * 1024) taint = PPW_RUN(false, true);
+      else if (area > rows_lds * 64) taint = PPW_RUN(true, true);
+      else taint = PPW_RUN(true, false);
+#undef PPW_RUN
+      if (taint) atomicOr(&fcnt[(size_t)(root / fpx) * C_COUNT + C_TAINT], taint);
+    }
+  }
+}
+
+// pp_flood_serial_kernel for every tainted frame at once: workgroup f redoes frame f alone through one heap, with the
+// frame's own marker order and push counter (its slab of the tall arrays is a contiguous [H + 1][W] image)
+__global__ __launch_bounds__(64) void ppb_flood_serial_kernel(
+    const float* __restrict__ img, const uint8_t* __restrict__ mask, const int32_t* __restrict__ markers,
+    unsigned long long* __restrict__ hkey, uint32_t* __restrict__ hidx, int32_t* __restrict__ out, const PPBatch b,
+    int32_t* __restrict__ fcnt) {
+  if (threadIdx.x != 0) return;
+  int32_t* fc = fcnt + (size_t)blockIdx.x * C_COUNT;
+  if (!fc[C_TAINT]) return;
+  const size_t base = (size_t)blockIdx.x * b.fpx;
+  const size_t n = (size_t)b.H * b.W;
+  const int32_t* mk = markers + base;
+  int32_t* o = out + base;
+  const float* im = img + base;
+  for (size_t i = 0; i < n; ++i) o[i] = mk[i];
+  PPHeap h;
+  h.key = hkey + base; h.idx = hidx + base; h.n = 0; h.taint = 0;
+  for (size_t i = 0; i < n; ++i)
+    if (mk[i] != 0) pp_push(h, pp_key(im[i], 0u), (uint32_t)i);
+  pp_flood<false>(h, im, mask + base, o, b.H, b.W, 0u);
+  fc[C_SCRATCH] = 1;
+}
+
+__global__ void ppb_finalize_kernel(const int32_t* __restrict__ out, uint16_t* __restrict__ labels, const PPBatch b,
+                                    const int32_t* __restrict__ fcnt, int32_t* __restrict__ n_inst,
+                                    int32_t* __restrict__ status) {
+  const int il = blockIdx.x * blockDim.x + threadIdx.x;
+  const int f = blockIdx.y;
+  const int n = b.H * b.W;
+  if (il < n) labels[(size_t)f * n + il] = (uint16_t)out[(size_t)f * b.fpx + il];
+  if (il == 0) {
+    const int32_t* fc = fcnt + (size_t)f * C_COUNT;
+    if (n_inst) n_inst[f] = fc[C_KEPT];
+    if (status) status[f] = (fc[C_SCRATCH] ? 1 : 0) | (fc[C_TAINT] ? 2 : 0) | (fc[C_TAINT] << 8);
+  }
+}
+
+extern "C" int mseg_distance_postprocess_batch(const float* border, const float* cell, int N, int H, int W,
+                                               long long row_stride, long long frame_stride, float th_cell, float th_seed,
+                                               int col_major_ids, uint16_t* labels, int32_t* n_instances_dev,
+                                               int32_t* status_dev, void* ws, size_t ws_bytes, void* stream) {
+  if (!border || !cell || !labels || !ws || N <= 0 || H <= 0 || W <= 0 || row_stride < W ||
+      (N > 1 && frame_stride < (long long)(H - 1) * row_stride + W))
+    return MSEG_EINVAL;
+  const size_t need = mseg_postproc_batch_workspace_bytes(N, H, W);
+  if (need == 0) return MSEG_EINVAL;
+  if (ws_bytes < need) return MSEG_EWORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  PPWs w;
+  int32_t* fcnt = nullptr;
+  ppb_carve(&w, &fcnt, ws, N, H, W);
+  const PPBatch b = {N, H, W, (H + 1) * W};
+  const int Ht = N * (H + 1);
+  const size_t n = (size_t)Ht * W;
+  const unsigned nb = pp_blocks(n);
+  const dim3 fgrid(pp_blocks((size_t)b.fpx), (unsigned)N), blk(PP_BLOCK);
+  double gw[3];
+  pp_gauss_weights(gw);
+  // gaussian of the cell map (read in place), thresholds; w.tmp = image of the flood (-smoothed cell)
+  hipLaunchKernelGGL(ppb_gauss_kernel, fgrid, blk, 0, st, cell, row_stride, frame_stride, w.tmp, b, 0, gw[0], gw[1], gw[2]);
+  hipLaunchKernelGGL(ppb_gauss_kernel, fgrid, blk, 0, st, (const float*)w.tmp, (long long)W, (long long)b.fpx, w.cs, b, 1,
+                     gw[0], gw[1], gw[2]);
+  hipLaunchKernelGGL(ppb_thresh_kernel, fgrid, blk, 0, st, border, row_stride, frame_stride, (const float*)w.cs, b, th_cell,
+                     th_seed, w.mask, w.seedb, w.tmp);
+  MSEG_LAUNCH_CHECK();
+  // the stages of pp_seeds_to_labels (distance rule, no forced serial flood) on the tall image
+  (void)hipMemsetAsync(w.counters, 0, sizeof(int32_t) * C_COUNT, st);
+  (void)hipMemsetAsync(fcnt, 0, sizeof(int32_t) * (size_t)N * C_COUNT, st);
+  (void)hipMemsetAsync(w.area, 0, sizeof(int32_t) * n, st);
+  (void)hipMemsetAsync(w.flag, 0, sizeof(int32_t) * n, st);
+  hipLaunchKernelGGL(pp_fill_kernel, dim3(nb), blk, 0, st, w.ckey, 0x7fffffff, n);
+  hipLaunchKernelGGL(pp_ccl_init_kernel, dim3(nb), blk, 0, st, (const uint8_t*)w.seedb, w.slab, n);
+  hipLaunchKernelGGL((pp_ccl_merge_kernel<true>), dim3(nb), blk, 0, st, (const uint8_t*)w.seedb, w.slab, Ht, W);
+  hipLaunchKernelGGL(pp_ccl_flatten_kernel, dim3(nb), blk, 0, st, w.slab, n);
+  hipLaunchKernelGGL(ppb_seed_stats_kernel, fgrid, blk, 0, st, (const int32_t*)w.slab, b, col_major_ids ? 1 : 0, w.area,
+                     w.ckey, fcnt);
+  hipLaunchKernelGGL(ppb_seed_totals_kernel, dim3((unsigned)N), dim3(64), 0, st, fcnt);
+  hipLaunchKernelGGL(ppb_seed_select_kernel, dim3(nb), blk, 0, st, (const int32_t*)w.slab, n, b.fpx, (const int32_t*)w.area,
+                     (const int32_t*)w.ckey, w.flag, fcnt);
+  MSEG_LAUNCH_CHECK();
+  if (pp_exclusive_scan(w.flag, w.scan, w.bsum, n, nullptr, st)) return MSEG_ELAUNCH;
+  hipLaunchKernelGGL(ppb_markers_kernel, dim3(nb), blk, 0, st, (const int32_t*)w.slab, n, b.fpx, (const int32_t*)w.area,
+                     (const int32_t*)w.ckey, (const int32_t*)w.scan, (const uint8_t*)w.mask, (const int32_t*)fcnt, w.markers,
+                     w.out);
+  hipLaunchKernelGGL(pp_ccl_init_kernel, dim3(nb), blk, 0, st, (const uint8_t*)w.mask, w.mlab, n);
+  hipLaunchKernelGGL((pp_ccl_merge_kernel<false>), dim3(nb), blk, 0, st, (const uint8_t*)w.mask, w.mlab, Ht, W);
+  hipLaunchKernelGGL(pp_ccl_flatten_kernel, dim3(nb), blk, 0, st, w.mlab, n);
+  (void)hipMemsetAsync(w.carea, 0, sizeof(int32_t) * n, st);
+  (void)hipMemsetAsync(w.hasm, 0, n, st);
+  (void)hipMemsetAsync(w.bymax, 0, sizeof(int32_t) * n, st);
+  (void)hipMemsetAsync(w.bxmax, 0, sizeof(int32_t) * n, st);
+  hipLaunchKernelGGL(pp_fill_kernel, dim3(nb), blk, 0, st, w.bymin, 0x7fffffff, n);
+  hipLaunchKernelGGL(pp_fill_kernel, dim3(nb), blk, 0, st, w.bxmin, 0x7fffffff, n);
+  hipLaunchKernelGGL(pp_mcomp_stats_kernel, dim3(nb), blk, 0, st, (const int32_t*)w.mlab, (const int32_t*)w.markers, Ht, W,
+                     w.carea, w.bymin, w.bymax, w.bxmin, w.bxmax, w.hasm);
+  hipLaunchKernelGGL(pp_mcomp_flag_kernel, dim3(nb), blk, 0, st, (const int32_t*)w.mlab, (const uint8_t*)w.hasm, n, w.flag,
+                     w.carea);
+  MSEG_LAUNCH_CHECK();
+  if (pp_exclusive_scan(w.carea, w.hoff, w.bsum, n, nullptr, st)) return MSEG_ELAUNCH;
+  if (pp_exclusive_scan(w.flag, w.scan, w.bsum, n, w.counters + C_NMCOMP, st)) return MSEG_ELAUNCH;
+  hipLaunchKernelGGL(pp_mcomp_list_kernel, dim3(nb), blk, 0, st, (const int32_t*)w.flag, (const int32_t*)w.scan, n, w.clist);
+  hipLaunchKernelGGL((ppb_flood_wave_kernel<PPW_TILE_S>), dim3(256 * 3), dim3(64), 0, st, (const float*)w.tmp,
+                     (const uint8_t*)w.mask, (const int32_t*)w.mlab, (const int32_t*)w.clist, (const int32_t*)w.hoff,
+                     (const int32_t*)w.carea, (const int32_t*)w.bymin, (const int32_t*)w.bymax, (const int32_t*)w.bxmin,
+                     (const int32_t*)w.bxmax, w.hkey, w.hidx, w.scan, w.out, Ht, W, w.counters, fcnt, b.fpx, (int)C_WORK_S,
+                     0LL, (long long)g_ppw_tile_s, g_ppw_tile_s, g_ppw_rows);
+  hipLaunchKernelGGL((ppb_flood_wave_kernel<PPW_TILE_L>), dim3(256), dim3(64), 0, st, (const float*)w.tmp,
+                     (const uint8_t*)w.mask, (const int32_t*)w.mlab, (const int32_t*)w.clist, (const int32_t*)w.hoff,
+                     (const int32_t*)w.carea, (const int32_t*)w.bymin, (const int32_t*)w.bymax, (const int32_t*)w.bxmin,
+                     (const int32_t*)w.bxmax, w.hkey, w.hidx, w.scan, w.out, Ht, W, w.counters, fcnt, b.fpx, (int)C_WORK_L,
+                     (long long)g_ppw_tile_s, 0x7fffffffffffffffLL, g_ppw_tile_l, g_ppw_rows);
+  hipLaunchKernelGGL(ppb_flood_serial_kernel, dim3((unsigned)N), dim3(64), 0, st, (const float*)w.tmp, (const uint8_t*)w.mask,
+                     (const int32_t*)w.markers, w.hkey, w.hidx, w.out, b, fcnt);
+  hipLaunchKernelGGL(ppb_finalize_kernel, dim3(pp_blocks((size_t)H * W), (unsigned)N), blk, 0, st, (const int32_t*)w.out,
+                     labels, b, (const int32_t*)fcnt, n_instances_dev, status_dev);
+  MSEG_LAUNCH_CHECK();
+  return MSEG_OK;
+}

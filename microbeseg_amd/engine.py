@@ -762,6 +762,23 @@ class RawFrame:
         return out
 
 
+def normalize_frames(raw, pad_top=0, pad_left=0):
+    """K14 for a group: raw (n, H0, W0) contiguous uint8 / uint16 (int16 storage) CUDA tensor -> the normalised, padded
+    network input (n, 1, H0 + pad_top, W0 + pad_left) fp32.  Every frame with its own extrema, two launches for the group
+    (mseg_frames_minmax, mseg_frames_normalize); same values bit for bit as RawFrame(frame).normalized()."""
+    if raw.dim() != 3 or raw.dtype not in RawFrame.PIX or not raw.is_cuda or not raw.is_contiguous():
+        raise RuntimeError("normalize_frames: a contiguous (n, H, W) uint8 / uint16 CUDA tensor expected")
+    lib = _lib.load()
+    n, h0, w0 = raw.shape
+    pix = RawFrame.PIX[raw.dtype]
+    minmax = torch.empty((n, 2), dtype=torch.int32, device=raw.device)
+    out = torch.empty((n, 1, h0 + int(pad_top), w0 + int(pad_left)), dtype=torch.float32, device=raw.device)
+    check(lib.mseg_frames_minmax(raw.data_ptr(), pix, n, h0 * w0, minmax.data_ptr(), _stream()), "frames_minmax")
+    check(lib.mseg_frames_normalize(raw.data_ptr(), pix, n, h0, w0, int(pad_top), int(pad_left), minmax.data_ptr(),
+                                    out.data_ptr(), _stream()), "frames_normalize")
+    return out
+
+
 def _first_layer_ok(cin, cout, stride):
     return stride == 1 and 1 <= cin <= 4 and cout % 4 == 0 and cout <= 256 and 256 % (cout // 4) == 0
 

@@ -30,6 +30,24 @@ def is_out_of_memory(err):
         "out of memory" in msg or "hiperroroutofmemory" in msg or "hip error: out of memory" in msg)
 
 
+FRAME_BATCH_PIXELS = 2048 * 2048     # pixels of one group of frames (see frame_batch_for)
+FRAME_BATCH_AUTO = 64
+
+
+def frame_batch_for(Hp, Wp, requested):
+    """Frames of padded size Hp x Wp that go through the network and the post-processing as ONE group:
+    ``max(1, min(requested, 2048 * 2048 // (Hp * Wp)))``; ``requested = 0`` means auto, i.e. ``min(64, ...)``.
+
+    Both constants are choices, not measurements: 2048^2 is the largest whole-frame size whose memory this project has
+    exercised, and a group of that many pixels has level-0 activations of the size of one such frame; 64 is the group
+    that fills this budget at 256^2.  Pure host arithmetic."""
+    cap = FRAME_BATCH_PIXELS // (int(Hp) * int(Wp))
+    req = int(requested)
+    if req <= 0:
+        req = FRAME_BATCH_AUTO
+    return max(1, min(req, cap))
+
+
 def load_model(model, device):
     """``model``: path of the checkpoint without/with suffix; reads ``<model>.json`` (architecture, label_type) and
     ``<model>.pth`` (state dict), like infer.py:83-84,119-131.  Returns (net in eval mode, model_settings)."""
@@ -66,6 +84,10 @@ class InferWorker(QObject):
     # checkpoints offline) predicts one confluent blob, whose flood is a single sequential component.
     prediction_hook = None
     BOUNDARY_BATCH = 8      # infer_stack, boundary method: frames whose floods share one launch (1..8)
+    # [extension] infer_stack: frames per group (one upload, one network forward at batch n, one batched post-processing
+    # call per group; frame_batch_for caps it by the frame size).  1 = frame by frame (the default: that path is untouched),
+    # 0 = auto.  Made for stacks of small frames (128^2 .. 512^2), where a frame's kernels are too short to fill the GPU.
+    frame_batch = 1
 
     def __init__(self, img_id_list=None, inference_path=None, omero_username=None, omero_password=None, omero_host=None,
                  omero_port=None, group_id=None,
@@ -165,6 +187,168 @@ class InferWorker(QObject):
                                          torch.cuda.current_stream().cuda_stream), "softmax3_hwc")
         return probs
 
+    def _normalized_padded(self, frame):
+        """one host frame -> (padded frame normalised with its own extrema, fp32, as inference() gets it; pads)"""
+        frame_min, frame_max = np.min(frame), np.max(frame)
+        padded, pads = self.pad_frame(np.copy(frame), frame_min)
+        return 2 * (padded.astype(np.float32) - frame_min) / (frame_max - frame_min) - 1, pads
+
+    def _group_input(self, frames):
+        """[n, H, W] host frames -> (network input (n, 1, Hp, Wp) fp32 on the device, pads).  uint8 / uint16: uploaded raw,
+        extrema and normalisation / padding per frame on the device; other dtypes: per frame on the host as inference()"""
+        if frames.dtype in (np.uint8, np.uint16) and max(frames.shape[1:]) <= 8192:
+            from ..utils.utils import pad_amounts
+            pads = pad_amounts(frames.shape[1:])
+            host = np.ascontiguousarray(frames)
+            raw = torch.from_numpy(host.view(np.int16) if host.dtype == np.uint16 else host).to(self.device)
+            return engine.normalize_frames(raw, pads[0], pads[1]), pads
+        xs, pads = [], [0, 0]
+        for frame in frames:
+            x, pads = self._normalized_padded(frame)
+            xs.append(x)
+        x = torch.from_numpy(np.ascontiguousarray(np.stack(xs)[:, None])).to(torch.float)
+        return x.to(self.device), pads
+
+    def forward_frames(self, frames):
+        """[n, H, W] host array -> the network's prediction for the n frames from ONE forward at batch n, on the device
+        (distance models: (border, cell), each (n, 1, Hp, Wp); boundary models: logits (n, 3, Hp, Wp); Hp x Wp = the padded
+        frame).  Every frame is normalised with its own minimum / maximum."""
+        frames = np.asarray(frames)
+        if frames.ndim != 3:
+            raise RuntimeError("forward_frames: a [n, H, W] array expected")
+        self.net.eval()
+        with torch.cuda.device(self.device), torch.no_grad():
+            x, _ = self._group_input(frames)
+            with engine.precision_scope(self.precision):
+                return self.net(x)
+
+    def _forward_group(self, x):
+        """network forward of a group (n, 1, Hp, Wp) -> list of (first frame, frames, prediction or None): one entry unless
+        the forward ran out of memory — then the group is halved and retried down to single frames, and a frame that does
+        not fit alone gets None (zero mask, like inference())"""
+        out, i, size = [], 0, x.shape[0]
+        while i < x.shape[0]:
+            m = min(size, x.shape[0] - i)
+            try:
+                with engine.precision_scope(self.precision):
+                    pred = self.net(x[i:i + m])
+            except (RuntimeError, MemoryError) as err:
+                if not is_out_of_memory(err):
+                    raise
+                del err
+                if self.device.type == 'cuda':
+                    torch.cuda.empty_cache()          # cached blocks of the failed attempt must not starve the retry
+                if m > 1:
+                    size = max(1, m // 2)
+                    continue
+                self.text_output.emit('RuntimeError during inference (maybe not enough ram/vram?)')
+                pred = None
+            out.append((i, m, pred))
+            i += m
+        return out, size
+
+    def _infer_stack_batched(self, img, results, fb, boundary):
+        """infer_stack with groups of ``fb`` frames: a group goes up through one of two pinned staging buffers on the copy
+        stream, its forward (batch n) runs on the main stream, its post-processing — one batched call for distance models,
+        the flood groups of at most 8 for boundary models — on the side stream, and its masks return through one pinned
+        buffer per group in flight (reused once the group is done).  Tensors that another stream still reads are kept
+        alive in ``pending`` until the group's event completed."""
+        T = len(img)
+        group_cap = fb
+        device_norm = img.dtype in (np.uint8, np.uint16)
+        from ..utils.utils import pad_amounts
+        pads = pad_amounts(img.shape[1:])
+        H, W = int(img.shape[1]), int(img.shape[2])
+        side = torch.cuda.Stream(device=self.device, priority=-1) if boundary else torch.cuda.Stream(device=self.device)
+        pending = []      # (first frame, frames, pinned host masks or None, event, tensors to keep alive)
+        free_hosts = []   # pinned [fb, H, W] mask buffers, handed back by finish(): one per group in flight, reused
+
+        def finish(entry):
+            f0, n, host, ev, _keep = entry
+            if ev is not None:
+                ev.synchronize()
+                results[f0:f0 + n] = host[:n].numpy().view(np.uint16)
+                free_hosts.append(host)
+            for f in range(f0, f0 + n):
+                self.progress.emit(int(100 * (f + 1) / T))
+
+        def launch_postproc(f0, n, pred):
+            if self.prediction_hook is not None:      # once per frame, in frame order, on that frame's (1, C, Hp, Wp) slice
+                if boundary:
+                    pred = torch.cat([self.prediction_hook(pred[i:i + 1]) for i in range(n)], dim=0)
+                else:
+                    hooked = [self.prediction_hook((pred[0][i:i + 1], pred[1][i:i + 1])) for i in range(n)]
+                    pred = (torch.cat([h[0] for h in hooked], dim=0), torch.cat([h[1] for h in hooked], dim=0))
+            ready = torch.cuda.Event()
+            ready.record()
+            host = free_hosts.pop() if free_hosts else torch.empty((group_cap, H, W), dtype=torch.int16, pin_memory=True)
+            with torch.cuda.stream(side):
+                side.wait_event(ready)
+                if boundary:
+                    logits = pred.contiguous()
+                    keep = [logits]
+                    for c0 in range(0, n, 8):
+                        probs = [self._softmax_hwc(logits[i:i + 1], pads) for i in range(c0, min(c0 + 8, n))]
+                        outs = pp.boundary_postprocessing_batch_device(probs, first_slot=0)
+                        for i, (labels, _, _) in enumerate(outs):
+                            host[c0 + i].copy_(labels, non_blocking=True)
+                        keep += [probs, outs]
+                else:
+                    border, cell = pred
+                    labels, _, _ = pp.distance_postprocessing_batch_device(border[:, 0], cell[:, 0], th_seed=self.ths[1],
+                                                                           th_cell=self.ths[0], pads=pads,
+                                                                           col_major_ids=True)
+                    host[:n].copy_(labels, non_blocking=True)
+                    keep = [border, cell, labels]
+                done = torch.cuda.Event()
+                done.record(side)
+            pending.append((f0, n, host, done, keep))
+
+        with torch.cuda.device(self.device), torch.no_grad():
+            shape = (fb, H, W) if device_norm else (fb, 1, H + pads[0], W + pads[1])
+            tdt = (torch.uint8 if img.dtype == np.uint8 else torch.int16) if device_norm else torch.float32
+            stage = [torch.empty(shape, dtype=tdt, pin_memory=True) for _ in range(2)]
+            dev_buf = [torch.empty(shape, dtype=tdt, device=self.device) for _ in range(2)]
+            uploaded, consumed = [None, None], [None, None]
+            copy_stream = torch.cuda.Stream(device=self.device)
+            main = torch.cuda.current_stream()
+            f0, g = 0, 0
+            while f0 < T and not self.stop_inference:
+                n = min(fb, T - f0)
+                k = g & 1
+                if uploaded[k] is not None:
+                    uploaded[k].synchronize()                # the staging buffer is free again
+                if device_norm:
+                    np.copyto(stage[k][:n].numpy().view(img.dtype), img[f0:f0 + n])
+                else:
+                    dst = stage[k].numpy()
+                    for i in range(n):
+                        dst[i, 0] = self._normalized_padded(img[f0 + i])[0]
+                with torch.cuda.stream(copy_stream):
+                    if consumed[k] is not None:
+                        copy_stream.wait_event(consumed[k])
+                    dev_buf[k][:n].copy_(stage[k][:n], non_blocking=True)
+                    uploaded[k] = torch.cuda.Event()
+                    uploaded[k].record(copy_stream)
+                main.wait_event(uploaded[k])
+                x = engine.normalize_frames(dev_buf[k][:n], pads[0], pads[1]) if device_norm else dev_buf[k][:n]
+                chunks, size = self._forward_group(x)
+                consumed[k] = torch.cuda.Event()
+                consumed[k].record(main)
+                fb = min(fb, size)                           # after an out-of-memory: smaller groups from here on
+                for c0, m, pred in chunks:
+                    if pred is None:
+                        pending.append((f0 + c0, m, None, None, None))
+                    else:
+                        launch_postproc(f0 + c0, m, pred)
+                while len(pending) > 2:                      # two groups in flight
+                    finish(pending.pop(0))
+                f0 += n
+                g += 1
+            while pending:
+                finish(pending.pop(0))
+        return results
+
     def infer_stack(self, img):
         """[T, H, W] stack -> [T, H, W] uint16 masks; per frame min/max + top/left padding exactly like
         infer_script_local.py:118-161 / infer.py:250-259.
@@ -177,6 +361,16 @@ class InferWorker(QObject):
         pipelined = (self.model_settings is not None and self.model_settings['label_type'] in ('distance', 'boundary')
                      and self.device.type == 'cuda')
         boundary = pipelined and self.model_settings['label_type'] == 'boundary'
+        if pipelined and int(self.frame_batch) != 1 and len(img) > 0:
+            if self.sliding_window:
+                self.text_output.emit('frame_batch is ignored with sliding-window inference')
+            elif max(img.shape[1:]) <= 8192:
+                from ..utils.utils import pad_amounts
+                pads = pad_amounts(img.shape[1:])
+                fb = frame_batch_for(img.shape[1] + pads[0], img.shape[2] + pads[1], self.frame_batch)
+                if fb > 1:
+                    self.net.eval()
+                    return self._infer_stack_batched(img, results, fb, boundary)
         if not pipelined:
             for frame in range(len(img)):
                 if self.stop_inference:

@@ -110,6 +110,46 @@ def distance_postprocessing_sweep_device(border, cell, ths, col_major_ids=True):
     return labels, info[0], info[1]
 
 
+_ws_batch_cache = {}
+
+
+def distance_postprocessing_batch_device(border, cell, th_seed, th_cell, pads=(0, 0), col_major_ids=True):
+    """N frames of one size in ONE chain of launches (mseg_distance_postprocess_batch).  border / cell: float32 CUDA
+    tensors (N, Hp, Wp) — or any view of that rank whose last dimension is dense, e.g. ``pred[:, 0]`` of the network's
+    (N, 1, Hp, Wp) output; ``pads`` = (rows, columns) of top / left padding, skipped IN PLACE through the strides (no
+    per-frame copy).  Returns (labels int16-view-of-uint16 (N, H, W), n_instances int32 (N,), status int32 (N,));
+    entry i equals distance_postprocessing_device on the un-padded frame i, bit for bit."""
+    lib = _lib.load()
+    if border.dim() != 3 or cell.dim() != 3 or border.shape != cell.shape:
+        raise RuntimeError("expected (N, Hp, Wp) predictions of one shape")
+    if border.dtype != torch.float32 or cell.dtype != torch.float32 or not cell.is_cuda:
+        raise RuntimeError("expected float32 CUDA tensors")
+    if cell.stride(2) != 1 or cell.stride() != border.stride():
+        border, cell = border.contiguous(), cell.contiguous()
+    N, Hp, Wp = cell.shape
+    pt, pl = int(pads[0]), int(pads[1])
+    H, W = Hp - pt, Wp - pl
+    dev = cell.device
+    need = lib.mseg_postproc_batch_workspace_bytes(N, H, W) if H > 0 and W > 0 else 0
+    if need == 0:
+        raise RuntimeError(f"unsupported group {N}x{H}x{W}")
+    key = (str(dev), _slot[0])      # its own entry per (device, slot): never shared with the one-frame calls
+    ws = _ws_batch_cache.get(key)
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        _ws_batch_cache[key] = ws
+    labels = torch.empty((N, H, W), dtype=torch.int16, device=dev)
+    info = torch.zeros((2, N), dtype=torch.int32, device=dev)
+    rs, fs = cell.stride(1), cell.stride(0)
+    off = (pt * rs + pl) * 4
+    _lib.check(lib.mseg_distance_postprocess_batch(border.data_ptr() + off, cell.data_ptr() + off, N, H, W, rs, fs,
+                                                   float(th_cell), float(th_seed), 1 if col_major_ids else 0,
+                                                   labels.data_ptr(), info[0].data_ptr(), info[1].data_ptr(),
+                                                   ws.data_ptr(), need, _stream()),
+               "distance_postprocess_batch")
+    return labels, info[0], info[1]
+
+
 def distance_postprocessing(border_prediction, cell_prediction, th_seed, th_cell):
     """ Post-processing for distance label (cell + neighbor) prediction (reference postprocessing.py:7).
 
