@@ -522,6 +522,34 @@ size_t mseg_overlay_workspace_bytes(void);
 int mseg_overlay_rgb(const void* img, int dtype, int T, int H, int W, int C, const uint8_t* outlines, uint8_t* out,
                      void* ws, size_t ws_bytes, void* stream);
 
+/* ---- training-set preparation (DataCropWorker src/utils/data_cropping.py:157-264,286,
+ * DataImportWorker src/utils/data_import.py:125-194, DataExportWorker src/utils/data_export.py:100-101) -----------------
+ * mseg_frame_stats: out[4] (device) = {min, max, sum v, sum v^2} of one uint8 / uint16 frame, exact, one pass (replaces
+ *   np.min / np.max / np.mean / np.std of data_cropping.py:172 and data_import.py:129-130; the host derives mean and std
+ *   from the integers).  npix < 2^31, so the sum of squares stays below 2^63.  64-bit integer atomics only.
+ * mseg_crops_extract: K crops of S x S out of one frame [H][W] in one launch, crop k starting at row origin_yx[2k], column
+ *   origin_yx[2k+1] (device); pixels beyond the frame take pad_value (the bottom / right padding of data_cropping.py:
+ *   178-180).  With f = f32(v), every operation rounded to fp32 in the order written:
+ *     crops_raw  [K][S][S] source dtype  v                                                    (data_cropping.py:261)
+ *     crops_show [K][S][S] uint8         trunc(255 * (f - lo) / (hi - lo))                    (data_cropping.py:205-206)
+ *     crops_u16  [K][S][S] uint16        trunc(clip(65535 * (f - lo) / (hi - lo), 0, 65535))  (data_export.py:100-101)
+ *     x          [K][1][S][S] fp32       2 * (f - lo) / (hi - lo) - 1                         (data_cropping.py:286)
+ *   Any output pointer may be NULL.  crops_show is meant for lo <= v <= hi (the frame's extrema).  hi <= lo: MSEG_EINVAL
+ *   (the reference divides by zero on a constant frame).
+ * mseg_crop_census: for the grid of ny x nx crops of S x S that starts at (y0, x0) inside a uint8 / uint16 label mask
+ *   [H][W]: cells[i] = distinct non-zero ids of crop i = h * nx + w (len(get_nucleus_ids(mask_crop))), area[i] = its
+ *   non-zero pixels (data_import.py:177-178); slot ny * nx holds both for the whole grid region (data_import.py:166; ids
+ *   span crops, so it is not the sum).  A 64-Kbit presence bitmap per crop in LDS, one in the workspace for the region.
+ * mseg_crops_overlay: rgb[K][S][S][3] = show replicated three times, outline pixels (255, 255, 0)
+ *   (data_cropping.py:214-215,238-240).                                                                                   */
+int mseg_frame_stats(const void* raw, int dtype, size_t npix, uint64_t* out, void* stream);
+int mseg_crops_extract(const void* raw, int dtype, int H, int W, int K, const int32_t* origin_yx, int S, int pad_value,
+                       int lo, int hi, void* crops_raw, uint8_t* crops_show, uint16_t* crops_u16, float* x, void* stream);
+size_t mseg_crop_census_workspace_bytes(void);
+int mseg_crop_census(const void* mask, int dtype, int H, int W, int y0, int x0, int ny, int nx, int S, int32_t* cells,
+                     int64_t* area, void* ws, size_t ws_bytes, void* stream);
+int mseg_crops_overlay(const uint8_t* show, const uint8_t* outlines, uint8_t* rgb, int K, int S, void* stream);
+
 /* ---- misc ---------------------------------------------------------------------------------------------------- */
 int mseg_version(void);
 const char* mseg_strerror(int code);

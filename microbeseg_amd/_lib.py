@@ -164,6 +164,11 @@ SIGNATURES = {
     "mseg_region_stats": (_I, [_P, _I, _I, _I, _P, C.c_int64, _P, _P, _P, _P, _P, _SZ, _P]),
     "mseg_overlay_workspace_bytes": (_SZ, []),
     "mseg_overlay_rgb": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _SZ, _P]),
+    "mseg_frame_stats": (_I, [_P, _I, _SZ, _P, _P]),
+    "mseg_crops_extract": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "mseg_crop_census_workspace_bytes": (_SZ, []),
+    "mseg_crop_census": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _SZ, _P]),
+    "mseg_crops_overlay": (_I, [_P, _P, _P, _I, _I, _P]),
     "mseg_version": (_I, []),
     "mseg_strerror": (C.c_char_p, [_I]),
     "mseg_last_hip_error": (_I, []),

@@ -200,6 +200,13 @@ __device__ __forceinline__ float ld_f1_rt(const void* base, size_t e, int bf16) 
 
 __device__ __forceinline__ float4 src_load4(const MsegSrc& s, size_t e) { return ld_f4_rt(s.ptr, e, s.dtype); }
 
+// K14, one pixel: 2 * (f32(x) - min) / (max - min) - 1 as numpy evaluates it on a float32 array with integer scalars
+// (infer.py:346-348, data_cropping.py:286).  Explicit round-to-nearest operations: no fused multiply-add.  Shared by the
+// frame normalisation (first.hip) and the crop extraction (prepare.hip), so both give the host formula's bits.
+__device__ __forceinline__ float raw_frame_norm(unsigned v, float fmin, float frange) {
+  return __fsub_rn(__fdiv_rn(__fmul_rn(2.f, __fsub_rn((float)v, fmin)), frange), 1.f);
+}
+
 // XCD-aware workgroup order (MI355X: 8 XCDs, each with a private L2; hardware deals consecutive workgroup ids
 // round-robin over the XCDs).  Maps the hardware id to a logical id such that each XCD works on one CONTIGUOUS range of
 // logical ids: workgroups that share an operand slab (neighbouring logical ids) then share an L2.  Bijective for any

@@ -79,10 +79,7 @@ struct RawFrame {
   int dtype, H0, W0, pad_top, pad_left;
 };
 
-__device__ __forceinline__ float raw_frame_norm(unsigned v, float fmin, float frange) {
-  // 2 * (f32(x) - min) / (max - min) - 1 as numpy evaluates it on a float32 array with integer scalars
-  return __fsub_rn(__fdiv_rn(__fmul_rn(2.f, __fsub_rn((float)v, fmin)), frange), 1.f);
-}
+// raw_frame_norm (common.h): 2 * (f32(x) - min) / (max - min) - 1, shared with csrc/prepare.hip
 __device__ __forceinline__ float raw_frame_px(const RawFrame& f, int yy, int xx, int H, int W, float fmin, float frange) {
   if ((unsigned)yy >= (unsigned)H || (unsigned)xx >= (unsigned)W) return 0.f;     // the convolution's zero padding
   const int y0 = yy - f.pad_top, x0 = xx - f.pad_left;
