@@ -183,6 +183,7 @@ int mseg_first_conv_fwd(const float* x4, const float* w, const float* bias, int 
 #define MSEG_PIX_U8 0
 #define MSEG_PIX_U16 1
 #define MSEG_PIX_I32 2 /* mseg_stack_relabel only */
+#define MSEG_PIX_F32 3 /* mseg_clahe_u16 only: fp32 holding the integers 0..65535 */
 int mseg_frame_minmax(const void* raw, int dtype, size_t npix, uint32_t* minmax, void* stream);
 int mseg_first_conv_fwd_raw(const void* raw, int dtype, int H0, int W0, int pad_top, int pad_left, const uint32_t* minmax,
                             const float* w, const float* bias, int Cout, void* z, int z_dtype, void* stream);
@@ -437,6 +438,19 @@ size_t mseg_aug_clahe_workspace_bytes(int N);
 int mseg_aug_clahe(const float* in, float* out, int N, int H, int W, const float* choice_dev, void* ws, void* stream);
 int mseg_aug_noise_normalize(const float* in, float* out, int N, int H, int W, const float* frac_dev,
                              const float* stats_dev, uint32_t seed, float vmin, float vmax, void* stream);
+
+/* ---- library-exact CLAHE (csrc/clahe.hip) -----------------------------------------------------------------
+ * (65535 * skimage.exposure.equalize_adapthist(img, clip_limit=0.01)).astype(np.uint16) of scikit-image 0.18.3, bit for
+ * bit, for N images [N][H][W] of one shape (src/training/mytransforms.py:92-95, src/inference/inference_dataset.py:63-77).
+ *   in:  uint8 (MSEG_PIX_U8, taken * 257 like img_as_uint), uint16 (MSEG_PIX_U16) or fp32 holding integers 0..65535
+ *        (MSEG_PIX_F32); out: uint16 (MSEG_PIX_U16) or fp32 (MSEG_PIX_F32) holding the uint16 result.
+ *   apply_dev: int32[N] on the device, 0 = copy the image through unchanged (the stored value; fp32 -> fp32 value-exact);
+ *        NULL = all images.  ws >= mseg_clahe_workspace_bytes(N, H, W) (0 for an unsupported shape).
+ *   MSEG_EINVAL: H or W < 8 (the tile H / 8 x W / 8 would be empty), H * W >= 2^31, N > 65535, a dtype not listed, in == out;
+ *   MSEG_EWORKSPACE: ws_bytes too small.  Nothing is launched in either case.                                          */
+size_t mseg_clahe_workspace_bytes(int N, int H, int W);
+int mseg_clahe_u16(const void* in, int in_dtype, int N, int H, int W, const int32_t* apply_dev, void* out, int out_dtype,
+                   void* ws, size_t ws_bytes, void* stream);
 
 /* ---- label creation for the boundary method (first part) --------------------------------------------
  * boundary_label (mode 0) / border_label (mode 1) of src/training/train_data_representations.py:75-125 for a batch of

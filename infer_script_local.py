@@ -5,7 +5,8 @@ Same flags and output as the reference ``infer_script_local.py`` (:17-25, :164-1
 ``--thresholds/-t`` (th_cell th_seed, default 0.10 0.45), ``--result_path/-r``, ``--channel/-c``, ``--device/-d``,
 ``--overwrite/-o``; writes ``mask_<stem>_channel<c>.tif`` (uint16, [T, H, W] squeezed); ``--export`` adds the files of
 the GUI's Export button (inference/result_export.py) for the segmented channel of uint8 / uint16 stacks;
-``--frame_batch N`` sends the frames of a stack through the network and the post-processing in groups of N.
+``--frame_batch N`` sends the frames of a stack through the network and the post-processing in groups of N;
+``--clahe`` enhances every uint8 / uint16 frame first, like the reference's ``ContrastEnhancement(apply_clahe=True)``.
 """
 import argparse
 from pathlib import Path
@@ -52,6 +53,11 @@ def main():
                         help='[extension] frames of a stack that share one upload, one network forward and one batched '
                              'post-processing call (made for stacks of small frames, 128-512 px; capped so that a group '
                              'holds at most 2048 x 2048 pixels; same masks for fp32). 1 = frame by frame, 0 = auto')
+    parser.add_argument('--clahe', default=False, action='store_true',
+                        help='[extension] contrast-enhance every frame on the device before it is normalised: the CLAHE of '
+                             'the reference\'s ContrastEnhancement(apply_clahe=True), i.e. scikit-image\'s '
+                             'equalize_adapthist(clip_limit=0.01), bit for bit; uint8 / uint16 images only, other stacks are '
+                             'segmented without it')
     parser.add_argument('--rois', default=False, action='store_true',
                         help='[extension] also write <mask file stem>_rois.json: one polygon ROI per cell and frame, the '
                              'records the OMERO route of infer_script.py uploads (traced on the device)')
@@ -82,6 +88,7 @@ def main():
                          sliding_window=args.sliding_window)
     worker.precision = args.precision
     worker.frame_batch = args.frame_batch
+    worker.apply_clahe = args.clahe
     worker.text_output.connect(print)
     torch.set_grad_enabled(False)
     print('--- Start inference ---')

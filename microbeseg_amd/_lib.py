@@ -16,6 +16,7 @@ MODE_CONV, MODE_TCONV = 0, 1
 EPI_PLAIN, EPI_SCATTER2X2 = 0, 1
 MORDER_LINEAR, MORDER_PARITY = 0, 1
 ST_F32, ST_BF16 = 0, 1      # tensor storage in HBM (MsegSrc.dtype, MsegIgemm.dst_dtype, `st` arguments)
+PIX_U8, PIX_U16, PIX_I32, PIX_F32 = 0, 1, 2, 3      # MSEG_PIX_*: pixel types of raw frames
 
 
 class MsegLibraryError(RuntimeError):
@@ -142,6 +143,8 @@ SIGNATURES = {
     "mseg_aug_clahe_workspace_bytes": (_SZ, [_I]),
     "mseg_aug_clahe": (_I, [_P, _P, _I, _I, _I, _P, _P, _P]),
     "mseg_aug_noise_normalize": (_I, [_P, _P, _I, _I, _I, _P, _P, C.c_uint32, _F, _F, _P]),
+    "mseg_clahe_workspace_bytes": (_SZ, [_I, _I, _I]),
+    "mseg_clahe_u16": (_I, [_P, _I, _I, _I, _I, _P, _P, _I, _P, _SZ, _P]),
     "mseg_label_boundary": (_I, [_P, _I, _I, _I, _I, _P, _P]),
     "mseg_label_distance_workspace_bytes": (_SZ, [_I, _I, _I]),
     "mseg_label_distance": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _SZ, _P]),

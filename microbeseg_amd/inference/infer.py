@@ -88,6 +88,9 @@ class InferWorker(QObject):
     # call per group; frame_batch_for caps it by the frame size).  1 = frame by frame (the default: that path is untouched),
     # 0 = auto.  Made for stacks of small frames (128^2 .. 512^2), where a frame's kernels are too short to fill the GPU.
     frame_batch = 1
+    # [extension] infer_stack: every uint8 / uint16 frame is contrast-enhanced on the device before its min / max
+    # (utils/clahe.py: the library-exact CLAHE of the reference's ContrastEnhancement) and goes on as a uint16 frame
+    apply_clahe = False
 
     def __init__(self, img_id_list=None, inference_path=None, omero_username=None, omero_password=None, omero_host=None,
                  omero_port=None, group_id=None,
@@ -247,7 +250,25 @@ class InferWorker(QObject):
             i += m
         return out, size
 
-    def _infer_stack_batched(self, img, results, fb, boundary):
+    def _clahe_enabled(self, img):
+        """apply_clahe for this stack?  Float stacks are segmented without it (no fixed grey-level range), with a message"""
+        if not self.apply_clahe:
+            return False
+        if img.dtype not in (np.uint8, np.uint16):
+            self.text_output.emit(f'Skip CLAHE (it needs uint8 / uint16 frames, got {img.dtype}): segmenting the frames as '
+                                  'they are')
+            return False
+        if self.device.type != 'cuda':
+            raise RuntimeError("apply_clahe runs on the GPU: there is no CPU path")
+        return True
+
+    def _clahe_host_frame(self, frame):
+        """one host frame -> its CLAHE, uint16, back on the host (the routes that normalise on the host)"""
+        from ..utils.clahe import equalize_adapthist_device
+        with torch.cuda.device(self.device):
+            return equalize_adapthist_device(np.ascontiguousarray(frame), device=self.device).cpu().numpy().view(np.uint16)
+
+    def _infer_stack_batched(self, img, results, fb, boundary, clahe=False):
         """infer_stack with groups of ``fb`` frames: a group goes up through one of two pinned staging buffers on the copy
         stream, its forward (batch n) runs on the main stream, its post-processing — one batched call for distance models,
         the flood groups of at most 8 for boundary models — on the side stream, and its masks return through one pinned
@@ -331,7 +352,14 @@ class InferWorker(QObject):
                     uploaded[k] = torch.cuda.Event()
                     uploaded[k].record(copy_stream)
                 main.wait_event(uploaded[k])
-                x = engine.normalize_frames(dev_buf[k][:n], pads[0], pads[1]) if device_norm else dev_buf[k][:n]
+                if device_norm:
+                    raw = dev_buf[k][:n]
+                    if clahe:                                # one call for the group; uint16 frames from here on
+                        from ..utils.clahe import clahe_device
+                        raw = clahe_device(raw)
+                    x = engine.normalize_frames(raw, pads[0], pads[1])
+                else:
+                    x = dev_buf[k][:n]
                 chunks, size = self._forward_group(x)
                 consumed[k] = torch.cuda.Event()
                 consumed[k].record(main)
@@ -361,6 +389,7 @@ class InferWorker(QObject):
         pipelined = (self.model_settings is not None and self.model_settings['label_type'] in ('distance', 'boundary')
                      and self.device.type == 'cuda')
         boundary = pipelined and self.model_settings['label_type'] == 'boundary'
+        clahe = self._clahe_enabled(img)
         if pipelined and int(self.frame_batch) != 1 and len(img) > 0:
             if self.sliding_window:
                 self.text_output.emit('frame_batch is ignored with sliding-window inference')
@@ -370,12 +399,12 @@ class InferWorker(QObject):
                 fb = frame_batch_for(img.shape[1] + pads[0], img.shape[2] + pads[1], self.frame_batch)
                 if fb > 1:
                     self.net.eval()
-                    return self._infer_stack_batched(img, results, fb, boundary)
+                    return self._infer_stack_batched(img, results, fb, boundary, clahe)
         if not pipelined:
             for frame in range(len(img)):
                 if self.stop_inference:
                     break
-                img_frame = np.copy(img[frame])
+                img_frame = self._clahe_host_frame(img[frame]) if clahe else np.copy(img[frame])
                 frame_min, frame_max = np.min(img_frame), np.max(img_frame)
                 img_frame, pads = self.pad_frame(img_frame, frame_min)
                 results[frame] = self.inference(img_frame, frame_min, frame_max, pads)
@@ -489,11 +518,16 @@ class InferWorker(QObject):
                         uploaded[k] = torch.cuda.Event()
                         uploaded[k].record(copy_stream)
                     main.wait_event(uploaded[k])
-                    pred = self._forward(engine.RawFrame(raw_dev[k], pads[0], pads[1]))
+                    raw = raw_dev[k]
+                    if clahe:                            # enhanced on the main stream; a uint16 frame from here on
+                        from ..utils.clahe import clahe_device
+                        raw = clahe_device(raw[None])[0]
+                    pred = self._forward(engine.RawFrame(raw, pads[0], pads[1]))
                     consumed[k] = torch.cuda.Event()
                     consumed[k].record(main)
                 else:
-                    img_frame = np.copy(img[frame])
+                    # (sliding-window inference comes here: the whole frame is enhanced before it is tiled)
+                    img_frame = self._clahe_host_frame(img[frame]) if clahe else np.copy(img[frame])
                     frame_min, frame_max = np.min(img_frame), np.max(img_frame)
                     img_frame, pads = self.pad_frame(img_frame, frame_min)
                     img_batch = 2 * (img_frame.astype(np.float32) - frame_min) / (frame_max - frame_min) - 1

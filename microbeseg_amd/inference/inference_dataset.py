@@ -2,8 +2,11 @@
 :13-41, pre_processing_transforms :44-62, Normalization :80-91, Padding :94-104, Scaling :107-125, ToTensor :128-140).
 
 Host code (numpy): per image ``2 * (f32(img) - min) / (max - min) - 1``, top/left padding with the minimum up to the
-next tested model input size, tensor (1, H, W).  CLAHE and down-scaling need scikit-image, which this stack does not
-ship; the evaluation (eval.py:121-122) uses neither (apply_clahe=False, scale_factor=1) and asking for them raises.
+next tested model input size, tensor (1, H, W).  ``apply_clahe=True`` enhances the image first, on the device, with the
+library-exact CLAHE of utils/clahe.py (the reference calls scikit-image's equalize_adapthist; same uint16 values) — in
+the loading process only, i.e. with ``num_workers=0``.  Down-scaling (``scale_factor < 1``) would need scikit-image's
+anti-aliased rescale, which this stack does not ship: nothing in the reference passes a factor other than 1, and asking
+for one raises.
 """
 import numpy as np
 import torch
@@ -51,8 +54,14 @@ class ContrastEnhancement(object):
 
     def __call__(self, sample):
         if self.apply_clahe:
-            raise RuntimeError("CLAHE pre-processing needs scikit-image (equalize_adapthist), which is outside the "
-                               "MI355X hot path; the evaluation runs with apply_clahe=False")
+            # inference_dataset.py:71-76: (65535 * equalize_adapthist(np.squeeze(img), clip_limit=0.01)).astype(np.uint16)
+            import torch.utils.data
+            if torch.utils.data.get_worker_info() is not None:
+                raise RuntimeError("ContrastEnhancement(apply_clahe=True) runs on the GPU, which a DataLoader worker process "
+                                   "must not open: use num_workers=0 with this transform")
+            from ..utils.clahe import equalize_adapthist_device
+            img = equalize_adapthist_device(np.squeeze(sample['image']))
+            sample['image'] = img.cpu().numpy().view(np.uint16)
         return sample
 
 

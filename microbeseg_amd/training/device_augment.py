@@ -15,9 +15,10 @@ pipeline to the whole batch in HBM (csrc/augment.hip).  What is kept from the re
     the image only; the output equals ToTensor's: image in [-1, 1] (min-max normalisation), labels unchanged in type.
 
 Differences (the reference pipeline is not numerically pinned — unseeded RNG, uint16 round trips between stages):
-intermediate images stay fp32 instead of being rounded to uint16 after every stage; the CLAHE branch of Contrast is
-Zuiderveld's algorithm with scikit-image's defaults (8 x 8 tiles, 256 bins, clip limit 0.01) without the library's
-padding / rounding details; imgaug's affine warps are reproduced with centre ((W-1)/2, (H-1)/2), bilinear / nearest sampling and a constant 0 border.
+intermediate images stay fp32 instead of being rounded to uint16 after every stage; the CLAHE branch of Contrast is, by
+default (``clahe='zuiderveld'``), Zuiderveld's algorithm with scikit-image's defaults (8 x 8 tiles, 256 bins, clip limit
+0.01) without the library's padding / rounding details — ``clahe='library'`` runs the library's routine bit for bit instead
+(csrc/clahe.hip: the image is integer-valued fp32 at that stage, so the result is exactly the reference's); imgaug's affine warps are reproduced with centre ((W-1)/2, (H-1)/2), bilinear / nearest sampling and a constant 0 border.
 """
 import ctypes as C
 import math
@@ -91,7 +92,12 @@ def rotation_matrices(deg, H, W):
 class DeviceAugment:
     """Callable: (img uint16 (N, H, W) on the device, list of label planes) -> (image fp32 (N, 1, H, W) in [-1, 1], labels)."""
 
-    def __init__(self, label_type, min_value, max_value, seed=None):
+    CLAHE_MODES = ('zuiderveld', 'library')
+
+    def __init__(self, label_type, min_value, max_value, seed=None, clahe='zuiderveld'):
+        if clahe not in self.CLAHE_MODES:
+            raise ValueError(f"DeviceAugment: clahe must be one of {self.CLAHE_MODES}, got {clahe!r}")
+        self.clahe = clahe
         self.label_type = label_type
         self.min_value, self.max_value = float(min_value), float(max_value)
         self._py = random.Random(seed) if seed is not None else random
@@ -134,7 +140,11 @@ class DeviceAugment:
                                                     par.data_ptr(), st), "aug_contrast_params")
             _lib.check(lib.mseg_aug_contrast(a.data_ptr(), b.data_ptr(), N, H, W, par.data_ptr(), st), "aug_contrast")
             a, b = b, a
-            if (params["contrast"][:, 0] == 3).any():
+            if (params["contrast"][:, 0] == 3).any() and self.clahe == 'library':
+                from ..utils.clahe import clahe_device
+                clahe_device(a, apply=up((params["contrast"][:, 0] == 3).astype(np.int32)), out=b)
+                a, b = b, a
+            elif (params["contrast"][:, 0] == 3).any():
                 cws = torch.empty(lib.mseg_aug_clahe_workspace_bytes(N), dtype=torch.uint8, device=dev)
                 _lib.check(lib.mseg_aug_clahe(a.data_ptr(), b.data_ptr(), N, H, W, choice.data_ptr(), cws.data_ptr(), st),
                            "aug_clahe")

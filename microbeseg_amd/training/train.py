@@ -292,7 +292,7 @@ class _Feeder:
     """One batch: pinned host tensors -> HBM, then (train phase only) the reference's Flip .. Noise + ToTensor pipeline
     on the device (training/device_augment.py)."""
 
-    def __init__(self, label_type, device, train_transform):
+    def __init__(self, label_type, device, train_transform, clahe='zuiderveld'):
         self.distance = label_type == 'distance'
         self.device = device
         self.augment = None
@@ -300,7 +300,7 @@ class _Feeder:
             if device.type != 'cuda':
                 raise RuntimeError("device augmentation needs the MI355X HIP path (no CPU fallback)")
             from .device_augment import DeviceAugment
-            self.augment = DeviceAugment(label_type, train_transform.min_value, train_transform.max_value)
+            self.augment = DeviceAugment(label_type, train_transform.min_value, train_transform.max_value, clahe=clahe)
 
     def __call__(self, samples, training):
         """-> (image batch, tuple of label batches)"""
@@ -349,6 +349,9 @@ class TrainWorker(QObject):
                             # 0.1-0.2 ms of host time per step instead of 7-18 ms.  Off by default: measured round 3, a step is
                             # GPU-bound even at batch 4 (bf16 8.0 ms eager with the weight gradients on a second stream,
                             # 8.7-8.8 ms replayed) — the replay buys host time (GUI thread, data loader), not throughput
+
+    augment_clahe = 'zuiderveld'    # CLAHE branch of the Contrast augmentation: 'library' = scikit-image's routine bit for bit
+                                    # (csrc/clahe.hip, what the reference computes), 'zuiderveld' = the earlier stand-in
 
     @pyqtSlot()
     def stop_training_process(self):
@@ -537,7 +540,8 @@ class TrainWorker(QObject):
                 if console:
                     print('{}'.format(console_line))
 
-        feeder = _Feeder(configs['label_type'], device, getattr(datasets['train'], 'transform', None))
+        feeder = _Feeder(configs['label_type'], device, getattr(datasets['train'], 'transform', None),
+                         clahe=self.augment_clahe)
         plans, loaders = self._loaders(datasets, configs, device, world, rank)
         criterion = get_loss(configs['loss'], label_type=configs['label_type'])
         regime = _Regime(configs['optimizer'], finetune, net.parameters(), configs['max_epochs'])

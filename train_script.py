@@ -5,7 +5,8 @@ Same flags as the reference ``train_script.py`` (:16-28): ``--omero_id/-id``, ``
 ``--iterations/-i`` (1), ``--method/-m`` (distance), ``--optimizer/-o`` (Ranger), ``--model_path/-r``,
 ``--device/-d`` (cuda:0), OMERO credentials.  Extensions: ``--train_path`` (a local, already exported + labelled
 training set ``<path>/{train,val}/{img,mask,cell_dist,neighbor_dist|boundary}_*.tif``),
-``--filters F0 F1`` and ``--max_epochs``.  Exporting a set from OMERO and creating the training labels
+``--filters F0 F1``, ``--max_epochs`` and ``--augment_clahe {zuiderveld,library}`` (``library``: the CLAHE branch of the
+Contrast augmentation computes exactly what the reference's scikit-image call does).  Exporting a set from OMERO and creating the training labels
 (reference train_script.py:41-114) are outside the hot path and need the reference's OMERO stack.
 Multi-GPU: ``python -m torch.distributed.run --nproc-per-node N train_script.py ...`` (one process per GPU, RCCL).
 """
@@ -34,6 +35,10 @@ def main():
     parser.add_argument('--max_epochs', default=None, type=int, help='[extension] epoch budget override')
     parser.add_argument('--precision', default='fp32', choices=['fp32', 'bf16'],
                         help='[extension] bf16 = bf16 matrix-core inputs, fp32 accumulate / storage / statistics')
+    parser.add_argument('--augment_clahe', default='zuiderveld', choices=['zuiderveld', 'library'],
+                        help='[extension] CLAHE branch of the Contrast augmentation: library = scikit-image\'s '
+                             'equalize_adapthist(clip_limit=0.01) bit for bit, as the reference computes it; zuiderveld = '
+                             'the textbook form this build used so far (the default for now)')
     args = parser.parse_args()
 
     if args.method not in ('boundary', 'distance'):
@@ -64,6 +69,7 @@ def main():
     from microbeseg_amd.training.train import TrainWorker
     worker = TrainWorker()
     worker.precision = args.precision
+    worker.augment_clahe = args.augment_clahe
     worker.start_training(path_data, model_path, args.method, args.iterations, args.optimizer.lower(), args.batch_size,
                           device, world, True, filters=args.filters, max_epochs=args.max_epochs)
     if world > 1:
