@@ -266,7 +266,8 @@ int mseg_norm_bwd(const void* gy, const void* z, int N, int HW, int C, int st, i
 
 /* MaxPool2d(2, 2) of a norm-on-load operand (pool_method = 'max': unets.py:306-307,363-364).  Forward writes the plain
  * pooled tensor [N][H/2][W/2][C]; backward routes gout to the first maximum of each window (torch's rule) and writes
- * (or accumulates into) gin = dL/d(normalised operand), [N][H][W][C].                                          */
+ * (or accumulates into) gin = dL/d(normalised operand), [N][H][W][C].  fp32 tensors only: H and W even, C % 4 == 0 and
+ * src->dtype == MSEG_ST_F32, otherwise MSEG_EINVAL and nothing is launched (there is no bf16-storage form).       */
 int mseg_maxpool2x2_fwd(const MsegSrc* src, int N, int H, int W, float* out, void* stream);
 int mseg_maxpool2x2_bwd(const MsegSrc* src, int N, int H, int W, const float* gout, float* gin, int accumulate,
                         void* stream);

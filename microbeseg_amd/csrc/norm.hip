@@ -1073,6 +1073,7 @@ __global__ void maxpool_bwd_kernel(const MsegSrc s, int N, int H, int W, const f
 
 extern "C" int mseg_maxpool2x2_fwd(const MsegSrc* src, int N, int H, int W, float* out, void* stream) {
   if (!src || !src->ptr || !out || N <= 0 || H <= 0 || W <= 0 || (H & 1) || (W & 1) || (src->C & 3)) return MSEG_EINVAL;
+  if (src->dtype != MSEG_ST_F32) return MSEG_EINVAL;      // the kernel reads float4: a bf16 source would be misread
   const size_t total = (size_t)N * (H / 2) * (W / 2) * (src->C / 4);
   hipLaunchKernelGGL(maxpool_fwd_kernel, dim3(nblocks(total, 8192u)), dim3(256), 0, (hipStream_t)stream, *src, N, H, W, out);
   MSEG_LAUNCH_CHECK();
@@ -1083,6 +1084,7 @@ extern "C" int mseg_maxpool2x2_bwd(const MsegSrc* src, int N, int H, int W, cons
                                    int accumulate, void* stream) {
   if (!src || !src->ptr || !gout || !gin || N <= 0 || H <= 0 || W <= 0 || (H & 1) || (W & 1) || (src->C & 3))
     return MSEG_EINVAL;
+  if (src->dtype != MSEG_ST_F32) return MSEG_EINVAL;
   const size_t total = (size_t)N * (H / 2) * (W / 2) * (src->C / 4);
   hipLaunchKernelGGL(maxpool_bwd_kernel, dim3(nblocks(total, 8192u)), dim3(256), 0, (hipStream_t)stream, *src, N, H, W,
                      gout, gin, accumulate);
