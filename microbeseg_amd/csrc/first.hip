@@ -69,13 +69,13 @@ __global__ __launch_bounds__(256) void first_conv_fwd_kernel(const float* __rest
 // ---- K14: frame normalisation on the device (reference: infer.py:346-348, infer_script_local.py:130-132) --------------------
 // The reference normalises a frame on the host, `2 * (img.astype(np.float32) - min) / (max - min) - 1` with min / max the
 // frame's extrema as scalars of the image dtype, after padding its top / left edge with `min` (utils.py:124-163) — i.e. pad
-// pixels become exactly -1.  Here the raw uint8 / uint16 frame is uploaded as it is, `frame_minmax_kernel` reduces the
+// pixels become exactly -1.  Here the raw uint8 / uint16 frame is uploaded as it is, `frames_minmax_kernel` reduces the
 // extrema on the device (integer atomics: order-independent) and the first convolution applies the same fp32 operations
 // in the same order while it loads its 3 x 3 window (explicit round-to-nearest operations: no fused multiply-add), so the
 // host never touches a pixel and no normalised or padded copy of the frame exists.
 struct RawFrame {
   const void* raw;               // [H0][W0] uint8 / uint16
-  const uint32_t* minmax;        // device: {~min, max} as written by frame_minmax_kernel
+  const uint32_t* minmax;        // device: {~min, max} as written by frames_minmax_kernel
   int dtype, H0, W0, pad_top, pad_left;
 };
 
@@ -90,12 +90,17 @@ __device__ __forceinline__ float raw_frame_px(const RawFrame& f, int yy, int xx,
   return raw_frame_norm(v, fmin, frange);
 }
 
-__global__ __launch_bounds__(256) void frame_minmax_kernel(const void* __restrict__ raw, int dtype, size_t n,
-                                                           uint32_t* __restrict__ minmax) {
+// N raw frames of one size, each with its OWN extrema (InferWorker.forward_frames); one frame is N = 1.  blockIdx.y = frame,
+// and a frame's grid does not depend on N, so every value is the one that the frame gets alone.  One launch for the group.
+__global__ __launch_bounds__(256) void frames_minmax_kernel(const void* __restrict__ raw, int dtype, size_t n,
+                                                            uint32_t* __restrict__ minmax) {
+  const size_t f = blockIdx.y;
+  const void* fr = dtype == MSEG_PIX_U8 ? (const void*)(reinterpret_cast<const uint8_t*>(raw) + f * n)
+                                        : (const void*)(reinterpret_cast<const uint16_t*>(raw) + f * n);
   unsigned lo = 0xffffffffu, hi = 0u;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-    const unsigned v = dtype == MSEG_PIX_U8 ? reinterpret_cast<const uint8_t*>(raw)[i]
-                                            : reinterpret_cast<const uint16_t*>(raw)[i];
+    const unsigned v = dtype == MSEG_PIX_U8 ? reinterpret_cast<const uint8_t*>(fr)[i]
+                                            : reinterpret_cast<const uint16_t*>(fr)[i];
     lo = v < lo ? v : lo;
     hi = v > hi ? v : hi;
   }
@@ -105,19 +110,28 @@ __global__ __launch_bounds__(256) void frame_minmax_kernel(const void* __restric
     lo = l2 < lo ? l2 : lo;
     hi = h2 > hi ? h2 : hi;
   }
-  if ((threadIdx.x & 63) == 0) {                       // both words start at 0: the minimum is kept inverted
-    atomicMax(minmax, ~lo);
-    atomicMax(minmax + 1, hi);
+  if ((threadIdx.x & 63) == 0) {
+    atomicMax(minmax + 2 * f, ~lo);
+    atomicMax(minmax + 2 * f + 1, hi);
   }
 }
 
-// the normalised, padded frame as an fp32 tensor [H][W] (networks whose first layer does not take the fused kernel below)
-__global__ __launch_bounds__(256) void frame_normalize_kernel(const RawFrame f, int H, int W, float* __restrict__ out) {
+__global__ __launch_bounds__(256) void frames_normalize_kernel(const void* __restrict__ raw, int dtype, int H0, int W0,
+                                                               int pad_top, int pad_left,
+                                                               const uint32_t* __restrict__ minmax, float* __restrict__ out) {
+  const size_t fi = blockIdx.y, n0 = (size_t)H0 * W0;
+  RawFrame f;
+  f.raw = dtype == MSEG_PIX_U8 ? (const void*)(reinterpret_cast<const uint8_t*>(raw) + fi * n0)
+                               : (const void*)(reinterpret_cast<const uint16_t*>(raw) + fi * n0);
+  f.minmax = minmax + 2 * fi;
+  f.dtype = dtype; f.H0 = H0; f.W0 = W0; f.pad_top = pad_top; f.pad_left = pad_left;
+  const int H = H0 + pad_top, W = W0 + pad_left;
   const float fmin = (float)(~f.minmax[0]), frange = (float)(f.minmax[1] - ~f.minmax[0]);
   const size_t n = (size_t)H * W;
+  float* o = out + fi * n;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
     const int yy = (int)(i / W), xx = (int)(i - (size_t)yy * W);
-    out[i] = raw_frame_px(f, yy, xx, H, W, fmin, frange);
+    o[i] = raw_frame_px(f, yy, xx, H, W, fmin, frange);
   }
 }
 
@@ -377,27 +391,38 @@ static int raw_frame_check(const void* raw, int dtype, int H0, int W0, int pad_t
   return MSEG_OK;
 }
 
-extern "C" int mseg_frame_minmax(const void* raw, int dtype, size_t npix, uint32_t* minmax, void* stream) {
-  if (!raw || !minmax || npix == 0 || (dtype != MSEG_PIX_U8 && dtype != MSEG_PIX_U16)) return MSEG_EINVAL;
+extern "C" int mseg_frames_minmax(const void* raw, int dtype, int N, size_t npix_per_frame, uint32_t* minmax, void* stream) {
+  if (!raw || !minmax || N <= 0 || N > 65535 || npix_per_frame == 0 || (dtype != MSEG_PIX_U8 && dtype != MSEG_PIX_U16))
+    return MSEG_EINVAL;
   hipStream_t st = (hipStream_t)stream;
-  if (hipMemsetAsync(minmax, 0, 2 * sizeof(uint32_t), st) != hipSuccess) return MSEG_ELAUNCH;
-  size_t blocks = (npix + 256 * 16 - 1) / (256 * 16);
+  if (hipMemsetAsync(minmax, 0, 2 * sizeof(uint32_t) * (size_t)N, st) != hipSuccess) return MSEG_ELAUNCH;
+  size_t blocks = (npix_per_frame + 256 * 16 - 1) / (256 * 16);
   if (blocks > 2048) blocks = 2048;
-  hipLaunchKernelGGL(frame_minmax_kernel, dim3((unsigned)blocks), dim3(256), 0, st, raw, dtype, npix, minmax);
+  hipLaunchKernelGGL(frames_minmax_kernel, dim3((unsigned)blocks, (unsigned)N), dim3(256), 0, st, raw, dtype, npix_per_frame,
+                     minmax);
   MSEG_LAUNCH_CHECK();
   return MSEG_OK;
 }
 
-extern "C" int mseg_frame_normalize(const void* raw, int dtype, int H0, int W0, int pad_top, int pad_left,
-                                    const uint32_t* minmax, float* out, void* stream) {
-  if (raw_frame_check(raw, dtype, H0, W0, pad_top, pad_left, minmax) || !out) return MSEG_EINVAL;
-  const RawFrame f = {raw, minmax, dtype, H0, W0, pad_top, pad_left};
+extern "C" int mseg_frames_normalize(const void* raw, int dtype, int N, int H0, int W0, int pad_top, int pad_left,
+                                     const uint32_t* minmax, float* out, void* stream) {
+  if (raw_frame_check(raw, dtype, H0, W0, pad_top, pad_left, minmax) || !out || N <= 0 || N > 65535) return MSEG_EINVAL;
   const int H = H0 + pad_top, W = W0 + pad_left;
   size_t blocks = ((size_t)H * W + 1023) / 1024;
   if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(frame_normalize_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, f, H, W, out);
+  hipLaunchKernelGGL(frames_normalize_kernel, dim3((unsigned)blocks, (unsigned)N), dim3(256), 0, (hipStream_t)stream, raw, dtype,
+                     H0, W0, pad_top, pad_left, minmax, out);
   MSEG_LAUNCH_CHECK();
   return MSEG_OK;
+}
+
+extern "C" int mseg_frame_minmax(const void* raw, int dtype, size_t npix, uint32_t* minmax, void* stream) {
+  return mseg_frames_minmax(raw, dtype, 1, npix, minmax, stream);
+}
+
+extern "C" int mseg_frame_normalize(const void* raw, int dtype, int H0, int W0, int pad_top, int pad_left,
+                                    const uint32_t* minmax, float* out, void* stream) {
+  return mseg_frames_normalize(raw, dtype, 1, H0, W0, pad_top, pad_left, minmax, out, stream);
 }
 
 extern "C" int mseg_first_conv_fwd_raw(const void* raw, int dtype, int H0, int W0, int pad_top, int pad_left,
@@ -453,77 +478,6 @@ extern "C" int mseg_first_wgrad(const float* x4, const void* dz, int dz_dtype, i
   MSEG_LAUNCH_CHECK();
   hipLaunchKernelGGL(first_wgrad_reduce_kernel, dim3((9 * Cout + 7) / 8), dim3(256), 0, st, (const float*)ws, blocks,
                      Cout, dW);
-  MSEG_LAUNCH_CHECK();
-  return MSEG_OK;
-}
-
-// ---- K14 for a GROUP of frames (InferWorker.forward_frames): N raw frames of one size, each with its OWN extrema -----------
-// blockIdx.y = frame; the same reduction / the same fp32 operations per pixel as the one-frame kernels above, so every value
-// is bit-identical to mseg_frame_minmax + mseg_frame_normalize of that frame alone.  One launch per function for the group.
-__global__ __launch_bounds__(256) void frames_minmax_kernel(const void* __restrict__ raw, int dtype, size_t n,
-                                                            uint32_t* __restrict__ minmax) {
-  const size_t f = blockIdx.y;
-  const void* fr = dtype == MSEG_PIX_U8 ? (const void*)(reinterpret_cast<const uint8_t*>(raw) + f * n)
-                                        : (const void*)(reinterpret_cast<const uint16_t*>(raw) + f * n);
-  unsigned lo = 0xffffffffu, hi = 0u;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-    const unsigned v = dtype == MSEG_PIX_U8 ? reinterpret_cast<const uint8_t*>(fr)[i]
-                                            : reinterpret_cast<const uint16_t*>(fr)[i];
-    lo = v < lo ? v : lo;
-    hi = v > hi ? v : hi;
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned l2 = __shfl_xor(lo, o, 64), h2 = __shfl_xor(hi, o, 64);
-    lo = l2 < lo ? l2 : lo;
-    hi = h2 > hi ? h2 : hi;
-  }
-  if ((threadIdx.x & 63) == 0) {
-    atomicMax(minmax + 2 * f, ~lo);
-    atomicMax(minmax + 2 * f + 1, hi);
-  }
-}
-
-__global__ __launch_bounds__(256) void frames_normalize_kernel(const void* __restrict__ raw, int dtype, int H0, int W0,
-                                                               int pad_top, int pad_left,
-                                                               const uint32_t* __restrict__ minmax, float* __restrict__ out) {
-  const size_t fi = blockIdx.y, n0 = (size_t)H0 * W0;
-  RawFrame f;
-  f.raw = dtype == MSEG_PIX_U8 ? (const void*)(reinterpret_cast<const uint8_t*>(raw) + fi * n0)
-                               : (const void*)(reinterpret_cast<const uint16_t*>(raw) + fi * n0);
-  f.minmax = minmax + 2 * fi;
-  f.dtype = dtype; f.H0 = H0; f.W0 = W0; f.pad_top = pad_top; f.pad_left = pad_left;
-  const int H = H0 + pad_top, W = W0 + pad_left;
-  const float fmin = (float)(~f.minmax[0]), frange = (float)(f.minmax[1] - ~f.minmax[0]);
-  const size_t n = (size_t)H * W;
-  float* o = out + fi * n;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-    const int yy = (int)(i / W), xx = (int)(i - (size_t)yy * W);
-    o[i] = raw_frame_px(f, yy, xx, H, W, fmin, frange);
-  }
-}
-
-extern "C" int mseg_frames_minmax(const void* raw, int dtype, int N, size_t npix_per_frame, uint32_t* minmax, void* stream) {
-  if (!raw || !minmax || N <= 0 || N > 65535 || npix_per_frame == 0 || (dtype != MSEG_PIX_U8 && dtype != MSEG_PIX_U16))
-    return MSEG_EINVAL;
-  hipStream_t st = (hipStream_t)stream;
-  if (hipMemsetAsync(minmax, 0, 2 * sizeof(uint32_t) * (size_t)N, st) != hipSuccess) return MSEG_ELAUNCH;
-  size_t blocks = (npix_per_frame + 256 * 16 - 1) / (256 * 16);
-  if (blocks > 2048) blocks = 2048;
-  hipLaunchKernelGGL(frames_minmax_kernel, dim3((unsigned)blocks, (unsigned)N), dim3(256), 0, st, raw, dtype, npix_per_frame,
-                     minmax);
-  MSEG_LAUNCH_CHECK();
-  return MSEG_OK;
-}
-
-extern "C" int mseg_frames_normalize(const void* raw, int dtype, int N, int H0, int W0, int pad_top, int pad_left,
-                                     const uint32_t* minmax, float* out, void* stream) {
-  if (raw_frame_check(raw, dtype, H0, W0, pad_top, pad_left, minmax) || !out || N <= 0 || N > 65535) return MSEG_EINVAL;
-  const int H = H0 + pad_top, W = W0 + pad_left;
-  size_t blocks = ((size_t)H * W + 1023) / 1024;
-  if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(frames_normalize_kernel, dim3((unsigned)blocks, (unsigned)N), dim3(256), 0, (hipStream_t)stream, raw, dtype,
-                     H0, W0, pad_top, pad_left, minmax, out);
   MSEG_LAUNCH_CHECK();
   return MSEG_OK;
 }

@@ -69,6 +69,54 @@ extern "C" size_t mseg_postproc_workspace_bytes(int H, int W) {
   return pp_carve(nullptr, nullptr, H, W);
 }
 
+// The frames of one call.  N frames of one size (mseg_distance_postprocess_batch) are laid out as one TALL image of
+// N * (H + 1) rows: frame f holds rows f * (H + 1) .. f * (H + 1) + H - 1, followed by one row whose mask and seeds are
+// zero.  Neither the 8-connected seed labelling nor the 4-connected flood can cross that row, so the connected-component,
+// prefix-sum, component-list and per-component flood stages run on the tall image as they are, in a number of launches
+// that does not depend on N (a stack of small frames spends its time between launches).  What depends on "the frame" is
+// a frame-aware kernel (grid: blocks over a slab x frames): the gaussian (reflects at frame borders, reads the prediction
+// in place through strides), the thresholds (write the tall layout), the seed statistics / totals / selection (the rule
+// area <= max(0.1 * mean, 4) uses the frame's mean), the id numbering (key within the frame, ids restart at 1), the taint
+// of the flood, the exact serial redo (one workgroup per tainted frame, over that frame alone: its push counter and marker
+// order are the frame's own — a serial flood over the tall image would interleave the frames' ages) and the finalize.
+// ONE frame (every other entry) is the same with N = 1 and a slab of exactly H * W pixels, no separator row.
+struct PPFrames {
+  int N, H, W;          // frames, un-padded frame size
+  int fpx;              // pixels of a frame's slab of the tall image: (H + 1) * W in a group, H * W for one frame
+  int32_t* fcnt;        // [N][C_COUNT] per-frame counters: C_PART, C_TOTAL, C_NCOMP, C_KEPT, C_TAINT, C_SCRATCH.  One frame:
+                        // `counters` itself, whose other slots (C_NMCOMP, C_WORK_*, C_SERIAL, C_CONST_*) are per call
+};
+
+static size_t ppb_carve(PPWs* w, int32_t** fcnt, void* base, int N, int H, int W) {
+  const size_t tall = pp_carve(w, base, N * (H + 1), W);
+  if (fcnt) *fcnt = (int32_t*)((char*)base + tall);
+  return align_up(tall + sizeof(int32_t) * (size_t)N * C_COUNT, 256);
+}
+
+// in-slab and in-frame indices are 32-bit: no more than 2^31 - 1 pixels per call, N is a grid dimension
+extern "C" size_t mseg_postproc_batch_workspace_bytes(int N, int H, int W) {
+  if (N <= 0 || N > 65535 || H <= 0 || W <= 0 || (long long)N * (H + 1) * W > 0x7fffffffLL) return 0;
+  return ppb_carve(nullptr, nullptr, nullptr, N, H, W);
+}
+
+// What an entry begins with: is the workspace there and large enough, then carve it.  N = 0: one frame on a workspace of
+// mseg_postproc_workspace_bytes; N >= 1: a group on one of mseg_postproc_batch_workspace_bytes.
+static int pp_open(PPWs* w, PPFrames* fr, void* ws, size_t ws_bytes, int N, int H, int W) {
+  if (!ws) return MSEG_EINVAL;
+  const size_t need = N ? mseg_postproc_batch_workspace_bytes(N, H, W) : mseg_postproc_workspace_bytes(H, W);
+  if (need == 0) return MSEG_EINVAL;
+  if (ws_bytes < need) return MSEG_EWORKSPACE;
+  if (N) {
+    int32_t* fcnt = nullptr;
+    ppb_carve(w, &fcnt, ws, N, H, W);
+    *fr = PPFrames{N, H, W, (H + 1) * W, fcnt};
+  } else {
+    pp_carve(w, ws, H, W);
+    *fr = PPFrames{1, H, W, H * W, w->counters};
+  }
+  return MSEG_OK;
+}
+
 static inline unsigned pp_blocks(size_t n) {
   size_t b = (n + PP_BLOCK - 1) / PP_BLOCK;
   return (unsigned)(b < 1 ? 1 : b);
@@ -84,19 +132,23 @@ __device__ __forceinline__ int pp_reflect(int i, int n) {
   return i;
 }
 
-__global__ void pp_gauss_kernel(const float* __restrict__ in, float* __restrict__ out, int H, int W, int axis,
-                                double w0, double w1, double w2) {
-  const size_t n = (size_t)H * W;
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const int y = (int)(i / W), x = (int)(i - (size_t)y * W);
+// in[f * fs + y * rs + x] (the prediction in place, or the tall layout), out in the tall layout; reflection inside the frame
+__global__ void pp_gauss_kernel(const float* __restrict__ in, long long rs, long long fs, float* __restrict__ out,
+                                const PPFrames fr, int axis, double w0, double w1, double w2) {
+  const unsigned il = blockIdx.x * blockDim.x + threadIdx.x;
+  if (il >= (unsigned)fr.fpx) return;
+  const int f = blockIdx.y, H = fr.H, W = fr.W;
+  const int y = (int)(il / (unsigned)W), x = (int)(il - (unsigned)y * W);
+  float* o = out + (size_t)f * fr.fpx + il;
+  if (y >= H) { *o = 0.f; return; }                                // the row between two frames
+  const float* p = in + (long long)f * fs;
   double c, m1, p1, m2, p2;
   if (axis == 0) {
-    c = in[i];
-    m2 = in[(size_t)pp_reflect(y - 2, H) * W + x]; p2 = in[(size_t)pp_reflect(y + 2, H) * W + x];
-    m1 = in[(size_t)pp_reflect(y - 1, H) * W + x]; p1 = in[(size_t)pp_reflect(y + 1, H) * W + x];
+    c = p[(long long)y * rs + x];
+    m2 = p[(long long)pp_reflect(y - 2, H) * rs + x]; p2 = p[(long long)pp_reflect(y + 2, H) * rs + x];
+    m1 = p[(long long)pp_reflect(y - 1, H) * rs + x]; p1 = p[(long long)pp_reflect(y + 1, H) * rs + x];
   } else {
-    const float* row = in + (size_t)y * W;
+    const float* row = p + (long long)y * rs;
     c = row[x];
     m2 = row[pp_reflect(x - 2, W)]; p2 = row[pp_reflect(x + 2, W)];
     m1 = row[pp_reflect(x - 1, W)]; p1 = row[pp_reflect(x + 1, W)];
@@ -105,16 +157,26 @@ __global__ void pp_gauss_kernel(const float* __restrict__ in, float* __restrict_
   double t = __dmul_rn(c, w2);
   t = __dadd_rn(t, __dmul_rn(__dadd_rn(m2, p2), w0));
   t = __dadd_rn(t, __dmul_rn(__dadd_rn(m1, p1), w1));
-  out[i] = (float)t;
+  *o = (float)t;
 }
 
 // ---- thresholds -----------------------------------------------------------------------------------------------
-__global__ void pp_distance_thresh_kernel(const float* __restrict__ border, const float* __restrict__ cs, size_t n,
-                                          float th_cell, float th_seed, uint8_t* __restrict__ mask,
-                                          uint8_t* __restrict__ seedb) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  float b = border[i];
+// mask and seeds in the tall layout; img (may be null: a threshold sweep needs it once per prediction): the flood's image, -cell
+__global__ void pp_distance_thresh_kernel(const float* __restrict__ border, long long rs, long long fs,
+                                          const float* __restrict__ cs, const PPFrames fr, float th_cell, float th_seed,
+                                          uint8_t* __restrict__ mask, uint8_t* __restrict__ seedb,
+                                          float* __restrict__ img) {
+  const unsigned il = blockIdx.x * blockDim.x + threadIdx.x;
+  if (il >= (unsigned)fr.fpx) return;
+  const int f = blockIdx.y, W = fr.W;
+  const int y = (int)(il / (unsigned)W), x = (int)(il - (unsigned)y * W);
+  const size_t i = (size_t)f * fr.fpx + il;
+  if (y >= fr.H) {                                 // the row between two frames
+    mask[i] = 0; seedb[i] = 0;
+    if (img) img[i] = 0.f;
+    return;
+  }
+  float b = border[(long long)f * fs + (long long)y * rs + x];
   b = b < 0.f ? 0.f : (b > 1.f ? 1.f : b);       // np.clip(border, 0, 1)
   const float c = cs[i];
   mask[i] = c > th_cell;
@@ -123,6 +185,7 @@ __global__ void pp_distance_thresh_kernel(const float* __restrict__ border, cons
   if (t < 0.05f) t = 0.f;
   t = t < 0.f ? 0.f : (t > 1.f ? 1.f : t);
   seedb[i] = __fsub_rn(c, t) > th_seed;
+  if (img) img[i] = -c;
 }
 
 __global__ void pp_boundary_thresh_kernel(const float* __restrict__ p, size_t n, uint8_t* __restrict__ mask,
@@ -138,11 +201,6 @@ __global__ void pp_boundary_thresh_kernel(const float* __restrict__ p, size_t n,
   mask[i] = m;
   seedb[i] = __fmul_rn(p1, __fsub_rn(1.f, p2)) > 0.5f;
   img[i] = m ? 1.f : 0.f;                        // watershed(image=mask): constant inside the mask
-}
-
-__global__ void pp_negate_kernel(const float* __restrict__ in, float* __restrict__ out, size_t n) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) out[i] = -in[i];
 }
 
 // ---- union-find connected components ------------------------------------------------------------------------------
@@ -216,17 +274,19 @@ __global__ void pp_fill_kernel(int32_t* __restrict__ a, int32_t v, size_t n) {
   if (i < n) a[i] = v;
 }
 
-__global__ void pp_seed_stats_kernel(const int32_t* __restrict__ L, int H, int W, int col_major,
-                                     int32_t* __restrict__ area, int32_t* __restrict__ ckey,
-                                     int32_t* __restrict__ counters) {
-  const size_t n = (size_t)H * W;
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int r = i < n ? L[i] : -1;
-  const int y = i < n ? (int)(i / W) : 0, x = i < n ? (int)(i - (size_t)y * W) : 0;
+// workgroups do not straddle frames (blockIdx.y = frame); keys are the frame's own
+__global__ void pp_seed_stats_kernel(const int32_t* __restrict__ L, const PPFrames fr, int col_major,
+                                     int32_t* __restrict__ area, int32_t* __restrict__ ckey) {
+  const unsigned il = blockIdx.x * blockDim.x + threadIdx.x;
+  const int f = blockIdx.y;
+  const bool in = il < (unsigned)fr.fpx;
+  const size_t i = (size_t)f * fr.fpx + il;
+  const int r = in ? L[i] : -1;
+  const int y = in ? (int)(il / (unsigned)fr.W) : 0, x = in ? (int)(il - (unsigned)y * fr.W) : 0;
   const int run = pp_run_length(r, x);
   if (run > 0) {                                            // first pixel of a horizontal run: the run's smallest key
     atomicAdd(&area[r], run);
-    atomicMin(&ckey[r], col_major ? x * H + y : (int)i);
+    atomicMin(&ckey[r], col_major ? x * fr.H + y : (int)il);
   }
   // the two frame-wide counts.  Atomics onto ONE address are served at ~10^8 per second: one per seed pixel, or even one
   // per wavefront (30 k), is what this kernel's time consisted of.  A workgroup combines its four waves in LDS and adds to
@@ -241,10 +301,11 @@ __global__ void pp_seed_stats_kernel(const int32_t* __restrict__ L, int H, int W
   }
   __syncthreads();
   if (threadIdx.x < 2 && sh_cnt[threadIdx.x])
-    atomicAdd(&counters[C_PART + 32 * threadIdx.x + (blockIdx.x & 31)], sh_cnt[threadIdx.x]);
+    atomicAdd(&fr.fcnt[(size_t)f * C_COUNT + C_PART + 32 * threadIdx.x + (blockIdx.x & 31)], sh_cnt[threadIdx.x]);
 }
 
-__global__ void pp_seed_totals_kernel(int32_t* __restrict__ counters) {
+__global__ void pp_seed_totals_kernel(int32_t* __restrict__ fcnt) {   // one workgroup per frame
+  int32_t* counters = fcnt + (size_t)blockIdx.x * C_COUNT;
   const int k = threadIdx.x >> 5, j = threadIdx.x & 31;           // 64 threads: [total | components] x 32 partials
   int v = counters[C_PART + 32 * k + j];
   for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -261,27 +322,31 @@ __device__ __forceinline__ bool pp_keep(int area, const int32_t* counters, int d
   return !((double)area <= min_area);
 }
 
-__global__ void pp_seed_select_kernel(const int32_t* __restrict__ L, size_t n, const int32_t* __restrict__ area,
-                                      const int32_t* __restrict__ ckey, int distance_rule,
-                                      int32_t* __restrict__ flag, int32_t* __restrict__ counters) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n || L[i] != (int)i) return;
-  if (pp_keep(area[i], counters, distance_rule)) {
-    flag[ckey[i]] = 1;
-    atomicAdd(&counters[C_KEPT], 1);
+__global__ void pp_seed_select_kernel(const int32_t* __restrict__ L, const PPFrames fr, const int32_t* __restrict__ area,
+                                      const int32_t* __restrict__ ckey, int distance_rule, int32_t* __restrict__ flag) {
+  const unsigned il = blockIdx.x * blockDim.x + threadIdx.x;
+  if (il >= (unsigned)fr.fpx) return;
+  const size_t fb = (size_t)blockIdx.y * fr.fpx, i = fb + il;
+  if (L[i] != (int)i) return;
+  int32_t* fc = fr.fcnt + (size_t)blockIdx.y * C_COUNT;
+  if (pp_keep(area[i], fc, distance_rule)) {
+    flag[fb + ckey[i]] = 1;
+    atomicAdd(&fc[C_KEPT], 1);
   }
 }
 
-__global__ void pp_markers_kernel(const int32_t* __restrict__ L, size_t n, const int32_t* __restrict__ area,
+// ids restart at 1 in every frame: rank among the kept seeds of the tall image minus the rank of the frame's first pixel
+__global__ void pp_markers_kernel(const int32_t* __restrict__ L, const PPFrames fr, const int32_t* __restrict__ area,
                                   const int32_t* __restrict__ ckey, const int32_t* __restrict__ scan,
-                                  const uint8_t* __restrict__ mask, int distance_rule,
-                                  const int32_t* __restrict__ counters, int32_t* __restrict__ markers,
+                                  const uint8_t* __restrict__ mask, int distance_rule, int32_t* __restrict__ markers,
                                   int32_t* __restrict__ out) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
+  const unsigned il = blockIdx.x * blockDim.x + threadIdx.x;
+  if (il >= (unsigned)fr.fpx) return;
+  const size_t fb = (size_t)blockIdx.y * fr.fpx, i = fb + il;
   int id = 0;
   const int r = L[i];
-  if (r >= 0 && mask[i] && pp_keep(area[r], counters, distance_rule)) id = scan[ckey[r]] + 1;   // markers * mask
+  if (r >= 0 && mask[i] && pp_keep(area[r], fr.fcnt + (size_t)blockIdx.y * C_COUNT, distance_rule))
+    id = scan[fb + ckey[r]] - scan[fb] + 1;                                                      // markers * mask
   markers[i] = id;
   out[i] = id;
 }
@@ -813,14 +878,17 @@ __device__ __forceinline__ int ppw_component(
 
 #define PPW_BIG_AREA 512      // components at least this large are started first (the longest one bounds the launch)
 
+// H: rows of the tall image.  counters: the call's (work queues, component count); the taint is the frame's.
+// The launch with the small tile takes the boxes of px_lo < pixels <= tile_px, the other one every box above px_lo.
+// (Few, narrow arguments on purpose: the kernel is at its scalar-register limit, and two more live registers cost 1.4 %.)
 template <int TILE_PX>
 __global__ __launch_bounds__(64) void pp_flood_wave_kernel(
     const float* __restrict__ img, const uint8_t* __restrict__ mask, const int32_t* __restrict__ mlab,
     const int32_t* __restrict__ clist, const int32_t* __restrict__ hoff, const int32_t* __restrict__ carea,
     const int32_t* __restrict__ bymin, const int32_t* __restrict__ bymax, const int32_t* __restrict__ bxmin,
     const int32_t* __restrict__ bxmax, unsigned long long* __restrict__ hkey, uint32_t* __restrict__ hidx,
-    int32_t* __restrict__ hlab, int32_t* out, int H, int W, int32_t* __restrict__ counters, int work_slot,
-    long long px_lo, long long px_hi, int tile_px, int rows_lds) {
+    int32_t* __restrict__ hlab, int32_t* out, int H, int W, int32_t* __restrict__ counters, int32_t* __restrict__ fcnt,
+    int fpx, int work_slot, int px_lo, int tile_px, int rows_lds) {
   __shared__ unsigned long long s_key[PPW_CAP];
   __shared__ uint32_t s_idx[PPW_CAP];
   __shared__ int32_t s_lab[PPW_CAP];
@@ -828,7 +896,6 @@ __global__ __launch_bounds__(64) void pp_flood_wave_kernel(
   if (counters[C_SERIAL]) return;                        // caller forces the exact serial path (boundary method)
   const int lane = threadIdx.x;
   const int ncomp = counters[C_NMCOMP];
-  int taint = 0;
   for (int pass = 0; pass < 2; ++pass) {
     for (;;) {
       int c = 0;
@@ -840,37 +907,45 @@ __global__ __launch_bounds__(64) void pp_flood_wave_kernel(
       if ((area >= PPW_BIG_AREA) != (pass == 0)) continue;
       const int y0 = bymin[root], y1 = bymax[root], x0 = bxmin[root], x1 = bxmax[root];
       const int th = y1 - y0 + 3, tw = x1 - x0 + 3;       // bounding box + 1 px rim
-      const long long px = (long long)th * tw;
-      if (px <= px_lo || px > px_hi) continue;            // the other launch's class
+      const long long pxl = (long long)th * tw;           // with the rim it can pass 2^31 - 1: larger than any tile, that is all
+      const int px = pxl > 0x7fffffffLL ? 0x7fffffff : (int)pxl;
+      if (px <= px_lo || (TILE_PX == PPW_TILE_S && px > tile_px)) continue;   // the other launch's class
       unsigned long long* gkey = hkey + hoff[root];
       uint32_t* gidx = hidx + hoff[root];
       int32_t* glab = hlab + hoff[root];
+      int taint;
 #define PPW_RUN(L, S) ppw_component<L, S>(s_key, s_idx, s_lab, s_tile, img, mask, mlab, gkey, gidx, glab, out, H, W, root, \
                                           y0, x0, th, tw, rows_lds)
-      if (px > (long long)tile_px || tw > 64 * 1024 || th > 32 * 1024) taint |= PPW_RUN(false, true);
-      else if (area > rows_lds * 64) taint |= PPW_RUN(true, true);
-      else taint |= PPW_RUN(true, false);                 // the queue can never outgrow its LDS rows
+      if (px > tile_px || tw > 64 * 1024 || th > 32 * 1024) taint = PPW_RUN(false, true);
+      else if (area > rows_lds * 64) taint = PPW_RUN(true, true);
+      else taint = PPW_RUN(true, false);                  // the queue can never outgrow its LDS rows
 #undef PPW_RUN
+      if (taint) atomicOr(&fcnt[(size_t)(root / fpx) * C_COUNT + C_TAINT], taint);   // a component lies inside one frame
     }
   }
-  if (taint) atomicOr(&counters[C_TAINT], taint);
 }
 
-// exact path: the whole image through ONE heap, exactly like the reference (single thread; correctness anchor)
-__global__ void pp_flood_serial_kernel(const float* __restrict__ img, const uint8_t* __restrict__ mask,
-                                       const int32_t* __restrict__ markers, unsigned long long* __restrict__ hkey,
-                                       uint32_t* __restrict__ hidx, int32_t* __restrict__ out, int H, int W,
-                                       int32_t* __restrict__ counters) {
-  if (blockIdx.x != 0 || threadIdx.x != 0) return;
-  if (!counters[C_SERIAL] && !counters[C_TAINT]) return;
-  const size_t n = (size_t)H * W;
-  for (size_t i = 0; i < n; ++i) out[i] = markers[i];    // discard whatever the fast path wrote
+// exact path: a whole frame through ONE heap, exactly like the reference (single thread; correctness anchor).  Workgroup f
+// redoes frame f if it is tainted, with the frame's own marker order and push counter (its slab of the tall arrays is a
+// contiguous image of at least H rows)
+__global__ __launch_bounds__(64) void pp_flood_serial_kernel(
+    const float* __restrict__ img, const uint8_t* __restrict__ mask, const int32_t* __restrict__ markers,
+    unsigned long long* __restrict__ hkey, uint32_t* __restrict__ hidx, int32_t* __restrict__ out, const PPFrames fr) {
+  if (threadIdx.x != 0) return;
+  int32_t* fc = fr.fcnt + (size_t)blockIdx.x * C_COUNT;
+  if (!fc[C_TAINT]) return;
+  const size_t base = (size_t)blockIdx.x * fr.fpx;
+  const size_t n = (size_t)fr.H * fr.W;
+  const int32_t* mk = markers + base;
+  int32_t* o = out + base;
+  const float* im = img + base;
+  for (size_t i = 0; i < n; ++i) o[i] = mk[i];           // discard whatever the fast path wrote
   PPHeap h;
-  h.key = hkey; h.idx = hidx; h.n = 0; h.taint = 0;
+  h.key = hkey + base; h.idx = hidx + base; h.n = 0; h.taint = 0;
   for (size_t i = 0; i < n; ++i)
-    if (markers[i] != 0) pp_push(h, pp_key(img[i], 0u), (uint32_t)i);
-  pp_flood<false>(h, img, mask, out, H, W, 0u);
-  counters[C_SCRATCH] = 1;                               // status bit 0: exact serial path was used
+    if (mk[i] != 0) pp_push(h, pp_key(im[i], 0u), (uint32_t)i);
+  pp_flood<false>(h, im, mask + base, o, fr.H, fr.W, 0u);
+  fc[C_SCRATCH] = 1;                                     // status bit 0: exact serial path was used
 }
 
 // Exact flood of a CONSTANT image (boundary method: watershed(image=mask, ...), every key ties on the value).
@@ -1570,15 +1645,18 @@ __global__ __launch_bounds__(PPC_THREADS) void pp_flood_const_bfs_multi_kernel(c
   pp_flood_const_bfs_body(p.mask, p.clist, p.hoff, p.out, H, W, p.counters);
 }
 
-__global__ void pp_finalize_kernel(const int32_t* __restrict__ out, uint16_t* __restrict__ labels, size_t n,
-                                   const int32_t* __restrict__ counters, int32_t* __restrict__ n_inst,
-                                   int32_t* __restrict__ status) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) labels[i] = (uint16_t)out[i];               // astype(np.uint16): wraps above 65535 like the reference
-  if (i == 0) {
-    if (n_inst) *n_inst = counters[C_KEPT];
+// labels: [N][H][W]
+__global__ void pp_finalize_kernel(const int32_t* __restrict__ out, uint16_t* __restrict__ labels, const PPFrames fr,
+                                   int32_t* __restrict__ n_inst, int32_t* __restrict__ status) {
+  const unsigned il = blockIdx.x * blockDim.x + threadIdx.x;
+  const unsigned n = (unsigned)fr.H * fr.W;
+  const int f = blockIdx.y;
+  if (il < n) labels[(size_t)f * n + il] = (uint16_t)out[(size_t)f * fr.fpx + il];   // astype(np.uint16): wraps like the reference
+  if (il == 0) {
+    const int32_t* fc = fr.fcnt + (size_t)f * C_COUNT;
+    if (n_inst) n_inst[f] = fc[C_KEPT];
     // bit0: exact serial flood used, bit1: tie taint, bits 8..12: which tie rule(s) fired (1, 2a, 2b, 3a, 3)
-    if (status) *status = (counters[C_SCRATCH] ? 1 : 0) | (counters[C_TAINT] ? 2 : 0) | (counters[C_TAINT] << 8);
+    if (status) status[f] = (fc[C_SCRATCH] ? 1 : 0) | (fc[C_TAINT] ? 2 : 0) | (fc[C_TAINT] << 8);
   }
 }
 
@@ -1594,21 +1672,24 @@ static void pp_gauss_weights(double w[3]) {
   w[0] = phi[0] / sum; w[1] = phi[1] / sum; w[2] = phi[2] / sum;
 }
 
-// shared tail: seeds (binary) + mask + image -> labels
+// shared tail: seeds (binary) + mask + image -> labels, all in the tall layout of `fr`
 // phase 0: everything; 1 (constant image only): up to the launches of the three constant-image flood bodies — which
 // mseg_boundary_flood_batch then makes for several frames at once; 2: what follows them
-static int pp_seeds_to_labels(const PPWs& w, const float* img, int H, int W, int distance_rule, int col_major,
+static int pp_seeds_to_labels(const PPWs& w, const PPFrames& fr, const float* img, int distance_rule, int col_major,
                               int force_serial, uint16_t* labels, int32_t* n_inst, int32_t* status, hipStream_t st,
                               int phase = 0) {
+  const int H = fr.N * (fr.fpx / fr.W), W = fr.W;        // the tall image
   const size_t n = (size_t)H * W;
   const unsigned nb = pp_blocks(n);
+  const dim3 fgrid(pp_blocks((size_t)fr.fpx), (unsigned)fr.N);      // the frame-aware kernels
+  const dim3 lgrid(pp_blocks((size_t)fr.H * fr.W), (unsigned)fr.N);
   if (phase == 2) {
-    hipLaunchKernelGGL(pp_finalize_kernel, dim3(nb), dim3(PP_BLOCK), 0, st, (const int32_t*)w.out, labels, n,
-                       (const int32_t*)w.counters, n_inst, status);
+    hipLaunchKernelGGL(pp_finalize_kernel, lgrid, dim3(PP_BLOCK), 0, st, (const int32_t*)w.out, labels, fr, n_inst, status);
     MSEG_LAUNCH_CHECK();
     return MSEG_OK;
   }
   (void)hipMemsetAsync(w.counters, 0, sizeof(int32_t) * C_COUNT, st);
+  if (fr.fcnt != w.counters) (void)hipMemsetAsync(fr.fcnt, 0, sizeof(int32_t) * (size_t)fr.N * C_COUNT, st);
   if (force_serial) hipLaunchKernelGGL(pp_fill_kernel, dim3(1), dim3(PP_BLOCK), 0, st, w.counters + C_SERIAL, 1, (size_t)1);
   (void)hipMemsetAsync(w.area, 0, sizeof(int32_t) * n, st);
   (void)hipMemsetAsync(w.flag, 0, sizeof(int32_t) * n, st);
@@ -1617,16 +1698,16 @@ static int pp_seeds_to_labels(const PPWs& w, const float* img, int H, int W, int
   hipLaunchKernelGGL(pp_ccl_init_kernel, dim3(nb), dim3(PP_BLOCK), 0, st, (const uint8_t*)w.seedb, w.slab, n);
   hipLaunchKernelGGL((pp_ccl_merge_kernel<true>), dim3(nb), dim3(PP_BLOCK), 0, st, (const uint8_t*)w.seedb, w.slab, H, W);
   hipLaunchKernelGGL(pp_ccl_flatten_kernel, dim3(nb), dim3(PP_BLOCK), 0, st, w.slab, n);
-  hipLaunchKernelGGL(pp_seed_stats_kernel, dim3(nb), dim3(PP_BLOCK), 0, st, (const int32_t*)w.slab, H, W, col_major,
-                     w.area, w.ckey, w.counters);
-  hipLaunchKernelGGL(pp_seed_totals_kernel, dim3(1), dim3(64), 0, st, w.counters);
-  hipLaunchKernelGGL(pp_seed_select_kernel, dim3(nb), dim3(PP_BLOCK), 0, st, (const int32_t*)w.slab, n,
-                     (const int32_t*)w.area, (const int32_t*)w.ckey, distance_rule, w.flag, w.counters);
+  hipLaunchKernelGGL(pp_seed_stats_kernel, fgrid, dim3(PP_BLOCK), 0, st, (const int32_t*)w.slab, fr, col_major, w.area,
+                     w.ckey);
+  hipLaunchKernelGGL(pp_seed_totals_kernel, dim3((unsigned)fr.N), dim3(64), 0, st, fr.fcnt);
+  hipLaunchKernelGGL(pp_seed_select_kernel, fgrid, dim3(PP_BLOCK), 0, st, (const int32_t*)w.slab, fr,
+                     (const int32_t*)w.area, (const int32_t*)w.ckey, distance_rule, w.flag);
   MSEG_LAUNCH_CHECK();
   if (pp_exclusive_scan(w.flag, w.scan, w.bsum, n, nullptr, st)) return MSEG_ELAUNCH;
-  hipLaunchKernelGGL(pp_markers_kernel, dim3(nb), dim3(PP_BLOCK), 0, st, (const int32_t*)w.slab, n,
+  hipLaunchKernelGGL(pp_markers_kernel, fgrid, dim3(PP_BLOCK), 0, st, (const int32_t*)w.slab, fr,
                      (const int32_t*)w.area, (const int32_t*)w.ckey, (const int32_t*)w.scan, (const uint8_t*)w.mask,
-                     distance_rule, (const int32_t*)w.counters, w.markers, w.out);
+                     distance_rule, w.markers, w.out);
   // 4-connected mask components -> independent floods
   hipLaunchKernelGGL(pp_ccl_init_kernel, dim3(nb), dim3(PP_BLOCK), 0, st, (const uint8_t*)w.mask, w.mlab, n);
   hipLaunchKernelGGL((pp_ccl_merge_kernel<false>), dim3(nb), dim3(PP_BLOCK), 0, st, (const uint8_t*)w.mask, w.mlab, H, W);
@@ -1650,14 +1731,13 @@ static int pp_seeds_to_labels(const PPWs& w, const float* img, int H, int W, int
   hipLaunchKernelGGL((pp_flood_wave_kernel<PPW_TILE_S>), dim3(256 * 3), dim3(64), 0, st, img, (const uint8_t*)w.mask,
                      (const int32_t*)w.mlab, (const int32_t*)w.clist, (const int32_t*)w.hoff, (const int32_t*)w.carea,
                      (const int32_t*)w.bymin, (const int32_t*)w.bymax, (const int32_t*)w.bxmin,
-                     (const int32_t*)w.bxmax, w.hkey, w.hidx, w.scan,
-                     w.out, H, W, w.counters, (int)C_WORK_S, 0LL, (long long)g_ppw_tile_s, g_ppw_tile_s, g_ppw_rows);
+                     (const int32_t*)w.bxmax, w.hkey, w.hidx, w.scan, w.out, H, W, w.counters, fr.fcnt, fr.fpx,
+                     (int)C_WORK_S, 0, g_ppw_tile_s, g_ppw_rows);
   hipLaunchKernelGGL((pp_flood_wave_kernel<PPW_TILE_L>), dim3(256), dim3(64), 0, st, img, (const uint8_t*)w.mask,
                      (const int32_t*)w.mlab, (const int32_t*)w.clist, (const int32_t*)w.hoff, (const int32_t*)w.carea,
                      (const int32_t*)w.bymin, (const int32_t*)w.bymax, (const int32_t*)w.bxmin,
-                     (const int32_t*)w.bxmax, w.hkey, w.hidx, w.scan,
-                     w.out, H, W, w.counters, (int)C_WORK_L, (long long)g_ppw_tile_s, 0x7fffffffffffffffLL, g_ppw_tile_l,
-                     g_ppw_rows);
+                     (const int32_t*)w.bxmax, w.hkey, w.hidx, w.scan, w.out, H, W, w.counters, fr.fcnt, fr.fpx,
+                     (int)C_WORK_L, g_ppw_tile_s, g_ppw_tile_l, g_ppw_rows);
   if (force_serial) {
     // constant image (boundary method): serial heap phase for the age-0 markers, then an ordered parallel BFS
     hipLaunchKernelGGL(pp_flood_const_flag_kernel, dim3(nb), dim3(PP_BLOCK), 0, st, (const int32_t*)w.markers, n, w.flag,
@@ -1683,34 +1763,36 @@ static int pp_seeds_to_labels(const PPWs& w, const float* img, int H, int W, int
     hipLaunchKernelGGL(pp_flood_const_bfs_kernel, dim3(1), dim3(PPC_THREADS), 0, st, (const uint8_t*)w.mask,
                        (uint32_t*)w.clist, (uint32_t*)w.hoff, w.out, H, W, (const int32_t*)w.counters);
   } else {
-    hipLaunchKernelGGL(pp_flood_serial_kernel, dim3(1), dim3(64), 0, st, img, (const uint8_t*)w.mask,
-                       (const int32_t*)w.markers, w.hkey, w.hidx, w.out, H, W, w.counters);
+    hipLaunchKernelGGL(pp_flood_serial_kernel, dim3((unsigned)fr.N), dim3(64), 0, st, img, (const uint8_t*)w.mask,
+                       (const int32_t*)w.markers, w.hkey, w.hidx, w.out, fr);
   }
-  hipLaunchKernelGGL(pp_finalize_kernel, dim3(nb), dim3(PP_BLOCK), 0, st, (const int32_t*)w.out, labels, n,
-                     (const int32_t*)w.counters, n_inst, status);
+  hipLaunchKernelGGL(pp_finalize_kernel, lgrid, dim3(PP_BLOCK), 0, st, (const int32_t*)w.out, labels, fr, n_inst, status);
   MSEG_LAUNCH_CHECK();
   return MSEG_OK;
 }
 
-static int pp_distance_smooth(const PPWs& w, const float* cell, int H, int W, hipStream_t st) {
-  const size_t n = (size_t)H * W;
-  const unsigned nb = pp_blocks(n);
+// cell (and border below): the prediction in place, frame f at + f * fs, rows rs apart
+static int pp_distance_smooth(const PPWs& w, const PPFrames& fr, const float* cell, long long rs, long long fs,
+                              hipStream_t st) {
+  const dim3 fgrid(pp_blocks((size_t)fr.fpx), (unsigned)fr.N), blk(PP_BLOCK);
   double gw[3];
   pp_gauss_weights(gw);
-  hipLaunchKernelGGL(pp_gauss_kernel, dim3(nb), dim3(PP_BLOCK), 0, st, cell, w.tmp, H, W, 0, gw[0], gw[1], gw[2]);
-  hipLaunchKernelGGL(pp_gauss_kernel, dim3(nb), dim3(PP_BLOCK), 0, st, (const float*)w.tmp, w.cs, H, W, 1, gw[0], gw[1], gw[2]);
-  hipLaunchKernelGGL(pp_negate_kernel, dim3(nb), dim3(PP_BLOCK), 0, st, (const float*)w.cs, w.tmp, n);  // image = -cell
+  hipLaunchKernelGGL(pp_gauss_kernel, fgrid, blk, 0, st, cell, rs, fs, w.tmp, fr, 0, gw[0], gw[1], gw[2]);
+  hipLaunchKernelGGL(pp_gauss_kernel, fgrid, blk, 0, st, (const float*)w.tmp, (long long)fr.W, (long long)fr.fpx, w.cs, fr, 1,
+                     gw[0], gw[1], gw[2]);
   MSEG_LAUNCH_CHECK();
   return MSEG_OK;
 }
 
-static int pp_distance_tail(const PPWs& w, const float* border, int H, int W, float th_cell, float th_seed,
-                            int col_major_ids, uint16_t* labels, int32_t* n_inst, int32_t* status, hipStream_t st) {
-  const size_t n = (size_t)H * W;
-  hipLaunchKernelGGL(pp_distance_thresh_kernel, dim3(pp_blocks(n)), dim3(PP_BLOCK), 0, st, border, (const float*)w.cs, n,
-                     th_cell, th_seed, w.mask, w.seedb);
+// write_img: w.tmp = image of the flood (-smoothed cell); it does not depend on the thresholds, so once per prediction
+static int pp_distance_tail(const PPWs& w, const PPFrames& fr, const float* border, long long rs, long long fs,
+                            float th_cell, float th_seed, bool write_img, int col_major_ids, uint16_t* labels,
+                            int32_t* n_inst, int32_t* status, hipStream_t st) {
+  hipLaunchKernelGGL(pp_distance_thresh_kernel, dim3(pp_blocks((size_t)fr.fpx), (unsigned)fr.N), dim3(PP_BLOCK), 0, st,
+                     border, rs, fs, (const float*)w.cs, fr, th_cell, th_seed, w.mask, w.seedb,
+                     write_img ? w.tmp : (float*)nullptr);
   MSEG_LAUNCH_CHECK();
-  return pp_seeds_to_labels(w, w.tmp, H, W, 1, col_major_ids, 0, labels, n_inst, status, st);
+  return pp_seeds_to_labels(w, fr, w.tmp, 1, col_major_ids, 0, labels, n_inst, status, st);
 }
 
 // Test / tuning hook: rows of the per-wave queue kept in LDS (1..16) and the two tile capacities in pixels (small <= 8192,
@@ -1733,15 +1815,14 @@ extern "C" int mseg_postproc_tuning(int heap_rows, int tile_small_px, int tile_l
 extern "C" int mseg_distance_postprocess(const float* border, const float* cell, int H, int W, float th_cell,
                                          float th_seed, int col_major_ids, uint16_t* labels, int32_t* n_instances_dev,
                                          int32_t* status_dev, void* ws, size_t ws_bytes, void* stream) {
-  if (!border || !cell || !labels || !ws || H <= 0 || W <= 0) return MSEG_EINVAL;
-  const size_t need = mseg_postproc_workspace_bytes(H, W);
-  if (need == 0) return MSEG_EINVAL;
-  if (ws_bytes < need) return MSEG_EWORKSPACE;
+  if (!border || !cell || !labels || H <= 0 || W <= 0) return MSEG_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   PPWs w;
-  pp_carve(&w, ws, H, W);
-  if (pp_distance_smooth(w, cell, H, W, st)) return MSEG_ELAUNCH;
-  return pp_distance_tail(w, border, H, W, th_cell, th_seed, col_major_ids, labels, n_instances_dev, status_dev, st);
+  PPFrames fr;
+  if (const int rc = pp_open(&w, &fr, ws, ws_bytes, 0, H, W)) return rc;
+  if (pp_distance_smooth(w, fr, cell, W, 0, st)) return MSEG_ELAUNCH;
+  return pp_distance_tail(w, fr, border, W, 0, th_cell, th_seed, true, col_major_ids, labels, n_instances_dev, status_dev,
+                          st);
 }
 
 // Threshold sweep of the evaluation (EvalWorker.inference: src/evaluation/eval.py:127-131,397-409 runs
@@ -1751,19 +1832,17 @@ extern "C" int mseg_distance_postprocess_sweep(const float* border, const float*
                                                const float* th_cell, const float* th_seed, int nth, int col_major_ids,
                                                uint16_t* labels, int32_t* n_instances_dev, int32_t* status_dev, void* ws,
                                                size_t ws_bytes, void* stream) {
-  if (!border || !cell || !labels || !ws || !th_cell || !th_seed || nth <= 0 || H <= 0 || W <= 0) return MSEG_EINVAL;
-  const size_t need = mseg_postproc_workspace_bytes(H, W);
-  if (need == 0) return MSEG_EINVAL;
-  if (ws_bytes < need) return MSEG_EWORKSPACE;
+  if (!border || !cell || !labels || !th_cell || !th_seed || nth <= 0 || H <= 0 || W <= 0) return MSEG_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   PPWs w;
-  pp_carve(&w, ws, H, W);
-  if (pp_distance_smooth(w, cell, H, W, st)) return MSEG_ELAUNCH;
+  PPFrames fr;
+  if (const int rc = pp_open(&w, &fr, ws, ws_bytes, 0, H, W)) return rc;
+  if (pp_distance_smooth(w, fr, cell, W, 0, st)) return MSEG_ELAUNCH;
   const size_t n = (size_t)H * W;
   for (int i = 0; i < nth; ++i) {
-    const int rc = pp_distance_tail(w, border, H, W, th_cell[i], th_seed[i], col_major_ids, labels + (size_t)i * n,
-                                    n_instances_dev ? n_instances_dev + i : nullptr, status_dev ? status_dev + i : nullptr,
-                                    st);
+    const int rc = pp_distance_tail(w, fr, border, W, 0, th_cell[i], th_seed[i], i == 0, col_major_ids,
+                                    labels + (size_t)i * n, n_instances_dev ? n_instances_dev + i : nullptr,
+                                    status_dev ? status_dev + i : nullptr, st);
     if (rc) return rc;
   }
   return MSEG_OK;
@@ -1772,37 +1851,33 @@ extern "C" int mseg_distance_postprocess_sweep(const float* border, const float*
 extern "C" int mseg_boundary_postprocess(const float* probs_hwc, int H, int W, uint16_t* labels,
                                          int32_t* n_instances_dev, int32_t* status_dev, void* ws, size_t ws_bytes,
                                          void* stream) {
-  if (!probs_hwc || !labels || !ws || H <= 0 || W <= 0) return MSEG_EINVAL;
-  const size_t need = mseg_postproc_workspace_bytes(H, W);
-  if (need == 0) return MSEG_EINVAL;
-  if (ws_bytes < need) return MSEG_EWORKSPACE;
+  if (!probs_hwc || !labels || H <= 0 || W <= 0) return MSEG_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   PPWs w;
-  pp_carve(&w, ws, H, W);
+  PPFrames fr;
+  if (const int rc = pp_open(&w, &fr, ws, ws_bytes, 0, H, W)) return rc;
   const size_t n = (size_t)H * W;
   hipLaunchKernelGGL(pp_boundary_thresh_kernel, dim3(pp_blocks(n)), dim3(PP_BLOCK), 0, st, probs_hwc, n, w.mask,
                      w.seedb, w.tmp);
   MSEG_LAUNCH_CHECK();
   // constant image: every key ties -> the order is the global heap's; go straight to the exact serial flood
-  return pp_seeds_to_labels(w, w.tmp, H, W, 0, 0, 1, labels, n_instances_dev, status_dev, st);
+  return pp_seeds_to_labels(w, fr, w.tmp, 0, 0, 1, labels, n_instances_dev, status_dev, st);
 }
 
 // The same in three calls, for several frames in flight (InferWorker.infer_stack): _pre (thresholds, components, marker list,
 // preorder ranks) per frame on its own workspace, ONE _flood_batch for up to 8 frames (one workgroup per frame), _post per
 // frame.  pre + flood_batch(B = 1) + post == mseg_boundary_postprocess, launch for launch.
 extern "C" int mseg_boundary_postprocess_pre(const float* probs_hwc, int H, int W, void* ws, size_t ws_bytes, void* stream) {
-  if (!probs_hwc || !ws || H <= 0 || W <= 0) return MSEG_EINVAL;
-  const size_t need = mseg_postproc_workspace_bytes(H, W);
-  if (need == 0) return MSEG_EINVAL;
-  if (ws_bytes < need) return MSEG_EWORKSPACE;
+  if (!probs_hwc || H <= 0 || W <= 0) return MSEG_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   PPWs w;
-  pp_carve(&w, ws, H, W);
+  PPFrames fr;
+  if (const int rc = pp_open(&w, &fr, ws, ws_bytes, 0, H, W)) return rc;
   const size_t n = (size_t)H * W;
   hipLaunchKernelGGL(pp_boundary_thresh_kernel, dim3(pp_blocks(n)), dim3(PP_BLOCK), 0, st, probs_hwc, n, w.mask,
                      w.seedb, w.tmp);
   MSEG_LAUNCH_CHECK();
-  return pp_seeds_to_labels(w, w.tmp, H, W, 0, 0, 1, nullptr, nullptr, nullptr, st, 1);
+  return pp_seeds_to_labels(w, fr, w.tmp, 0, 0, 1, nullptr, nullptr, nullptr, st, 1);
 }
 
 extern "C" int mseg_boundary_flood_batch(void* const* ws_list, int B, int H, int W, void* stream) {
@@ -1830,13 +1905,11 @@ extern "C" int mseg_boundary_flood_batch(void* const* ws_list, int B, int H, int
 
 extern "C" int mseg_boundary_postprocess_post(int H, int W, uint16_t* labels, int32_t* n_instances_dev, int32_t* status_dev,
                                               void* ws, size_t ws_bytes, void* stream) {
-  if (!labels || !ws || H <= 0 || W <= 0) return MSEG_EINVAL;
-  const size_t need = mseg_postproc_workspace_bytes(H, W);
-  if (need == 0) return MSEG_EINVAL;
-  if (ws_bytes < need) return MSEG_EWORKSPACE;
+  if (!labels || H <= 0 || W <= 0) return MSEG_EINVAL;
   PPWs w;
-  pp_carve(&w, ws, H, W);
-  return pp_seeds_to_labels(w, w.tmp, H, W, 0, 0, 1, labels, n_instances_dev, status_dev, (hipStream_t)stream, 2);
+  PPFrames fr;
+  if (const int rc = pp_open(&w, &fr, ws, ws_bytes, 0, H, W)) return rc;
+  return pp_seeds_to_labels(w, fr, w.tmp, 0, 0, 1, labels, n_instances_dev, status_dev, (hipStream_t)stream, 2);
 }
 
 // =====================================================================================================================
@@ -2064,309 +2137,20 @@ extern "C" int mseg_stack_relabel(const void* values, int dtype, int T, int H, i
 }
 
 // =====================================================================================================================
-// Distance post-processing of N frames of one size in ONE chain of launches (mseg_distance_postprocess_batch).
-// A stack of small frames (microfluidic chambers: 128^2 .. 512^2) spends its time between launches: the chain above is ~45
-// launches / memsets per frame over a few tens of thousands of pixels.  Here the N frames are laid out as one TALL image
-// of N * (H + 1) rows: frame f holds rows f * (H + 1) .. f * (H + 1) + H - 1, followed by one row whose mask and seeds are
-// zero.  Neither the 8-connected seed labelling nor the 4-connected flood can cross that row, so the connected-component,
-// prefix-sum, component-list and per-component flood stages run on the tall image as they are; what depends on "the frame"
-// has a frame-aware kernel below: the gaussian (reflects at frame borders, reads the prediction in place through strides),
-// the thresholds (write the tall layout), the seed statistics / totals / selection (the rule area <= max(0.1 * mean, 4) uses
-// the frame's mean: every frame has its own counter block, laid out like `counters`), the id numbering (key within the
-// frame, ids restart at 1), the taint of the flood (per frame), the exact serial redo (one workgroup per tainted frame,
-// over that frame alone: its push counter and marker order are the frame's own — a serial flood over the tall image would
-// interleave the frames' ages) and the finalize.  The number of launches does not depend on N.
-struct PPBatch {
-  int N, H, W;          // frames, un-padded frame size
-  int fpx;              // (H + 1) * W: pixels of a frame's slab of the tall image
-};
-
-static size_t ppb_carve(PPWs* w, int32_t** fcnt, void* base, int N, int H, int W) {
-  const size_t tall = pp_carve(w, base, N * (H + 1), W);
-  if (fcnt) *fcnt = (int32_t*)((char*)base + tall);
-  return align_up(tall + sizeof(int32_t) * (size_t)N * C_COUNT, 256);
-}
-
-extern "C" size_t mseg_postproc_batch_workspace_bytes(int N, int H, int W) {
-  if (N <= 0 || N > 65535 || H <= 0 || W <= 0 || (long long)N * (H + 1) * W > 0x7fffffffLL) return 0;
-  return ppb_carve(nullptr, nullptr, nullptr, N, H, W);
-}
-
-// one axis of the gaussian for every frame: in[f * fs + y * rs + x] (the prediction in place, or the tall layout),
-// out in the tall layout; same operations as pp_gauss_kernel, reflection inside the frame
-__global__ void ppb_gauss_kernel(const float* __restrict__ in, long long rs, long long fs, float* __restrict__ out,
-                                 const PPBatch b, int axis, double w0, double w1, double w2) {
-  const int il = blockIdx.x * blockDim.x + threadIdx.x;
-  if (il >= b.fpx) return;
-  const int f = blockIdx.y, H = b.H, W = b.W;
-  const int y = il / W, x = il - y * W;
-  float* o = out + (size_t)f * b.fpx + il;
-  if (y >= H) { *o = 0.f; return; }                                // the row between two frames
-  const float* fr = in + (long long)f * fs;
-  double c, m1, p1, m2, p2;
-  if (axis == 0) {
-    c = fr[(long long)y * rs + x];
-    m2 = fr[(long long)pp_reflect(y - 2, H) * rs + x]; p2 = fr[(long long)pp_reflect(y + 2, H) * rs + x];
-    m1 = fr[(long long)pp_reflect(y - 1, H) * rs + x]; p1 = fr[(long long)pp_reflect(y + 1, H) * rs + x];
-  } else {
-    const float* row = fr + (long long)y * rs;
-    c = row[x];
-    m2 = row[pp_reflect(x - 2, W)]; p2 = row[pp_reflect(x + 2, W)];
-    m1 = row[pp_reflect(x - 1, W)]; p1 = row[pp_reflect(x + 1, W)];
-  }
-  double t = __dmul_rn(c, w2);
-  t = __dadd_rn(t, __dmul_rn(__dadd_rn(m2, p2), w0));
-  t = __dadd_rn(t, __dmul_rn(__dadd_rn(m1, p1), w1));
-  *o = (float)t;
-}
-
-// pp_distance_thresh_kernel + pp_negate_kernel for every frame: mask, seeds and the flood's image (-cell) in the tall layout
-__global__ void ppb_thresh_kernel(const float* __restrict__ border, long long rs, long long fs,
-                                  const float* __restrict__ cs, const PPBatch bt, float th_cell, float th_seed,
-                                  uint8_t* __restrict__ mask, uint8_t* __restrict__ seedb, float* __restrict__ img) {
-  const int il = blockIdx.x * blockDim.x + threadIdx.x;
-  if (il >= bt.fpx) return;
-  const int f = blockIdx.y, W = bt.W;
-  const int y = il / W, x = il - y * W;
-  const size_t i = (size_t)f * bt.fpx + il;
-  if (y >= bt.H) { mask[i] = 0; seedb[i] = 0; img[i] = 0.f; return; }
-  float b = border[(long long)f * fs + (long long)y * rs + x];
-  b = b < 0.f ? 0.f : (b > 1.f ? 1.f : b);
-  const float c = cs[i];
-  mask[i] = c > th_cell;
-  const float b2 = __fmul_rn(b, b);
-  float t = (float)tan((double)b2);
-  if (t < 0.05f) t = 0.f;
-  t = t < 0.f ? 0.f : (t > 1.f ? 1.f : t);
-  seedb[i] = __fsub_rn(c, t) > th_seed;
-  img[i] = -c;
-}
-
-// pp_seed_stats_kernel per frame: workgroups do not straddle frames (blockIdx.y = frame), keys are the frame's own
-__global__ void ppb_seed_stats_kernel(const int32_t* __restrict__ L, const PPBatch b, int col_major,
-                                      int32_t* __restrict__ area, int32_t* __restrict__ ckey, int32_t* __restrict__ fcnt) {
-  const int il = blockIdx.x * blockDim.x + threadIdx.x;
-  const int f = blockIdx.y;
-  const bool in = il < b.fpx;
-  const size_t i = (size_t)f * b.fpx + il;
-  const int r = in ? L[i] : -1;
-  const int y = in ? il / b.W : 0, x = in ? il - y * b.W : 0;
-  const int run = pp_run_length(r, x);
-  if (run > 0) {
-    atomicAdd(&area[r], run);
-    atomicMin(&ckey[r], col_major ? x * b.H + y : il);
-  }
-  __shared__ int sh_cnt[2];
-  if (threadIdx.x < 2) sh_cnt[threadIdx.x] = 0;
-  __syncthreads();
-  const unsigned long long seeds = __ballot(r >= 0), roots = __ballot(r >= 0 && r == (int)i);
-  if ((threadIdx.x & 63) == 0) {
-    if (seeds) atomicAdd(&sh_cnt[0], __popcll(seeds));
-    if (roots) atomicAdd(&sh_cnt[1], __popcll(roots));
-  }
-  __syncthreads();
-  if (threadIdx.x < 2 && sh_cnt[threadIdx.x])
-    atomicAdd(&fcnt[(size_t)f * C_COUNT + C_PART + 32 * threadIdx.x + (blockIdx.x & 31)], sh_cnt[threadIdx.x]);
-}
-
-__global__ void ppb_seed_totals_kernel(int32_t* __restrict__ fcnt) {
-  int32_t* counters = fcnt + (size_t)blockIdx.x * C_COUNT;
-  const int k = threadIdx.x >> 5, j = threadIdx.x & 31;
-  int v = counters[C_PART + 32 * k + j];
-  for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  if (j == 0) counters[k == 0 ? C_TOTAL : C_NCOMP] = v;
-}
-
-__global__ void ppb_seed_select_kernel(const int32_t* __restrict__ L, size_t n, int fpx, const int32_t* __restrict__ area,
-                                       const int32_t* __restrict__ ckey, int32_t* __restrict__ flag,
-                                       int32_t* __restrict__ fcnt) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n || L[i] != (int)i) return;
-  const size_t f = i / (size_t)fpx;
-  int32_t* fc = fcnt + f * C_COUNT;
-  if (pp_keep(area[i], fc, 1)) {
-    flag[f * (size_t)fpx + ckey[i]] = 1;
-    atomicAdd(&fc[C_KEPT], 1);
-  }
-}
-
-// ids restart at 1 in every frame: rank among the kept seeds of the tall image minus the rank of the frame's first pixel
-__global__ void ppb_markers_kernel(const int32_t* __restrict__ L, size_t n, int fpx, const int32_t* __restrict__ area,
-                                   const int32_t* __restrict__ ckey, const int32_t* __restrict__ scan,
-                                   const uint8_t* __restrict__ mask, const int32_t* __restrict__ fcnt,
-                                   int32_t* __restrict__ markers, int32_t* __restrict__ out) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  int id = 0;
-  const int r = L[i];
-  if (r >= 0 && mask[i]) {
-    const size_t f = i / (size_t)fpx, fb = f * (size_t)fpx;
-    if (pp_keep(area[r], fcnt + f * C_COUNT, 1)) id = scan[fb + ckey[r]] - scan[fb] + 1;
-  }
-  markers[i] = id;
-  out[i] = id;
-}
-
-// pp_flood_wave_kernel with the taint kept per frame (a component lies inside one frame: root / fpx).  KEEP IN STEP with
-// pp_flood_wave_kernel: the body is that kernel's, line for line, except for where the taint goes and the C_SERIAL early
-// exit (the batch has no forced-serial mode); the one-frame kernel is left as it is so that its code does not change.
-template <int TILE_PX>
-__global__ __launch_bounds__(64) void ppb_flood_wave_kernel(
-    const float* __restrict__ img, const uint8_t* __restrict__ mask, const int32_t* __restrict__ mlab,
-    const int32_t* __restrict__ clist, const int32_t* __restrict__ hoff, const int32_t* __restrict__ carea,
-    const int32_t* __restrict__ bymin, const int32_t* __restrict__ bymax, const int32_t* __restrict__ bxmin,
-    const int32_t* __restrict__ bxmax, unsigned long long* __restrict__ hkey, uint32_t* __restrict__ hidx,
-    int32_t* __restrict__ hlab, int32_t* out, int H, int W, int32_t* __restrict__ counters, int32_t* __restrict__ fcnt,
-    int fpx, int work_slot, long long px_lo, long long px_hi, int tile_px, int rows_lds) {
-  __shared__ unsigned long long s_key[PPW_CAP];
-  __shared__ uint32_t s_idx[PPW_CAP];
-  __shared__ int32_t s_lab[PPW_CAP];
-  __shared__ uint32_t s_tile[TILE_PX];
-  const int lane = threadIdx.x;
-  const int ncomp = counters[C_NMCOMP];
-  for (int pass = 0; pass < 2; ++pass) {
-    for (;;) {
-      int c = 0;
-      if (lane == 0) c = atomicAdd(&counters[work_slot + pass], 1);
-      c = __builtin_amdgcn_readfirstlane(c);
-      if (c >= ncomp) break;
-      const int root = clist[c];
-      const int area = carea[root];
-      if ((area >= PPW_BIG_AREA) != (pass == 0)) continue;
-      const int y0 = bymin[root], y1 = bymax[root], x0 = bxmin[root], x1 = bxmax[root];
-      const int th = y1 - y0 + 3, tw = x1 - x0 + 3;
-      const long long px = (long long)th * tw;
-      if (px <= px_lo || px > px_hi) continue;
-      unsigned long long* gkey = hkey + hoff[root];
-      uint32_t* gidx = hidx + hoff[root];
-      int32_t* glab = hlab + hoff[root];
-      int taint;
-#define PPW_RUN(L, S) ppw_component<L, S>(s_key, s_idx, s_lab, s_tile, img, mask, mlab, gkey, gidx, glab, out, H, W, root, \
-                                          y0, x0, th, tw, rows_lds)
-      if (px > (long long)tile_px || tw > 64 * 1024 || th > 32 * 1024) taint = PPW_RUN(false, true);
-      else if (area > rows_lds * 64) taint = PPW_RUN(true, true);
-      else taint = PPW_RUN(true, false);
-#undef PPW_RUN
-      if (taint) atomicOr(&fcnt[(size_t)(root / fpx) * C_COUNT + C_TAINT], taint);
-    }
-  }
-}
-
-// pp_flood_serial_kernel for every tainted frame at once: workgroup f redoes frame f alone through one heap, with the
-// frame's own marker order and push counter (its slab of the tall arrays is a contiguous [H + 1][W] image)
-__global__ __launch_bounds__(64) void ppb_flood_serial_kernel(
-    const float* __restrict__ img, const uint8_t* __restrict__ mask, const int32_t* __restrict__ markers,
-    unsigned long long* __restrict__ hkey, uint32_t* __restrict__ hidx, int32_t* __restrict__ out, const PPBatch b,
-    int32_t* __restrict__ fcnt) {
-  if (threadIdx.x != 0) return;
-  int32_t* fc = fcnt + (size_t)blockIdx.x * C_COUNT;
-  if (!fc[C_TAINT]) return;
-  const size_t base = (size_t)blockIdx.x * b.fpx;
-  const size_t n = (size_t)b.H * b.W;
-  const int32_t* mk = markers + base;
-  int32_t* o = out + base;
-  const float* im = img + base;
-  for (size_t i = 0; i < n; ++i) o[i] = mk[i];
-  PPHeap h;
-  h.key = hkey + base; h.idx = hidx + base; h.n = 0; h.taint = 0;
-  for (size_t i = 0; i < n; ++i)
-    if (mk[i] != 0) pp_push(h, pp_key(im[i], 0u), (uint32_t)i);
-  pp_flood<false>(h, im, mask + base, o, b.H, b.W, 0u);
-  fc[C_SCRATCH] = 1;
-}
-
-__global__ void ppb_finalize_kernel(const int32_t* __restrict__ out, uint16_t* __restrict__ labels, const PPBatch b,
-                                    const int32_t* __restrict__ fcnt, int32_t* __restrict__ n_inst,
-                                    int32_t* __restrict__ status) {
-  const int il = blockIdx.x * blockDim.x + threadIdx.x;
-  const int f = blockIdx.y;
-  const int n = b.H * b.W;
-  if (il < n) labels[(size_t)f * n + il] = (uint16_t)out[(size_t)f * b.fpx + il];
-  if (il == 0) {
-    const int32_t* fc = fcnt + (size_t)f * C_COUNT;
-    if (n_inst) n_inst[f] = fc[C_KEPT];
-    if (status) status[f] = (fc[C_SCRATCH] ? 1 : 0) | (fc[C_TAINT] ? 2 : 0) | (fc[C_TAINT] << 8);
-  }
-}
-
+// Distance post-processing of N frames of one size in ONE chain of launches (the tall layout: PPFrames).  border / cell are
+// read in place: frame f at + f * frame_stride, rows row_stride apart.  labels: [N][H][W]; n_instances / status: [N].
 extern "C" int mseg_distance_postprocess_batch(const float* border, const float* cell, int N, int H, int W,
                                                long long row_stride, long long frame_stride, float th_cell, float th_seed,
                                                int col_major_ids, uint16_t* labels, int32_t* n_instances_dev,
                                                int32_t* status_dev, void* ws, size_t ws_bytes, void* stream) {
-  if (!border || !cell || !labels || !ws || N <= 0 || H <= 0 || W <= 0 || row_stride < W ||
+  if (!border || !cell || !labels || N <= 0 || H <= 0 || W <= 0 || row_stride < W ||
       (N > 1 && frame_stride < (long long)(H - 1) * row_stride + W))
     return MSEG_EINVAL;
-  const size_t need = mseg_postproc_batch_workspace_bytes(N, H, W);
-  if (need == 0) return MSEG_EINVAL;
-  if (ws_bytes < need) return MSEG_EWORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   PPWs w;
-  int32_t* fcnt = nullptr;
-  ppb_carve(&w, &fcnt, ws, N, H, W);
-  const PPBatch b = {N, H, W, (H + 1) * W};
-  const int Ht = N * (H + 1);
-  const size_t n = (size_t)Ht * W;
-  const unsigned nb = pp_blocks(n);
-  const dim3 fgrid(pp_blocks((size_t)b.fpx), (unsigned)N), blk(PP_BLOCK);
-  double gw[3];
-  pp_gauss_weights(gw);
-  // gaussian of the cell map (read in place), thresholds; w.tmp = image of the flood (-smoothed cell)
-  hipLaunchKernelGGL(ppb_gauss_kernel, fgrid, blk, 0, st, cell, row_stride, frame_stride, w.tmp, b, 0, gw[0], gw[1], gw[2]);
-  hipLaunchKernelGGL(ppb_gauss_kernel, fgrid, blk, 0, st, (const float*)w.tmp, (long long)W, (long long)b.fpx, w.cs, b, 1,
-                     gw[0], gw[1], gw[2]);
-  hipLaunchKernelGGL(ppb_thresh_kernel, fgrid, blk, 0, st, border, row_stride, frame_stride, (const float*)w.cs, b, th_cell,
-                     th_seed, w.mask, w.seedb, w.tmp);
-  MSEG_LAUNCH_CHECK();
-  // the stages of pp_seeds_to_labels (distance rule, no forced serial flood) on the tall image
-  (void)hipMemsetAsync(w.counters, 0, sizeof(int32_t) * C_COUNT, st);
-  (void)hipMemsetAsync(fcnt, 0, sizeof(int32_t) * (size_t)N * C_COUNT, st);
-  (void)hipMemsetAsync(w.area, 0, sizeof(int32_t) * n, st);
-  (void)hipMemsetAsync(w.flag, 0, sizeof(int32_t) * n, st);
-  hipLaunchKernelGGL(pp_fill_kernel, dim3(nb), blk, 0, st, w.ckey, 0x7fffffff, n);
-  hipLaunchKernelGGL(pp_ccl_init_kernel, dim3(nb), blk, 0, st, (const uint8_t*)w.seedb, w.slab, n);
-  hipLaunchKernelGGL((pp_ccl_merge_kernel<true>), dim3(nb), blk, 0, st, (const uint8_t*)w.seedb, w.slab, Ht, W);
-  hipLaunchKernelGGL(pp_ccl_flatten_kernel, dim3(nb), blk, 0, st, w.slab, n);
-  hipLaunchKernelGGL(ppb_seed_stats_kernel, fgrid, blk, 0, st, (const int32_t*)w.slab, b, col_major_ids ? 1 : 0, w.area,
-                     w.ckey, fcnt);
-  hipLaunchKernelGGL(ppb_seed_totals_kernel, dim3((unsigned)N), dim3(64), 0, st, fcnt);
-  hipLaunchKernelGGL(ppb_seed_select_kernel, dim3(nb), blk, 0, st, (const int32_t*)w.slab, n, b.fpx, (const int32_t*)w.area,
-                     (const int32_t*)w.ckey, w.flag, fcnt);
-  MSEG_LAUNCH_CHECK();
-  if (pp_exclusive_scan(w.flag, w.scan, w.bsum, n, nullptr, st)) return MSEG_ELAUNCH;
-  hipLaunchKernelGGL(ppb_markers_kernel, dim3(nb), blk, 0, st, (const int32_t*)w.slab, n, b.fpx, (const int32_t*)w.area,
-                     (const int32_t*)w.ckey, (const int32_t*)w.scan, (const uint8_t*)w.mask, (const int32_t*)fcnt, w.markers,
-                     w.out);
-  hipLaunchKernelGGL(pp_ccl_init_kernel, dim3(nb), blk, 0, st, (const uint8_t*)w.mask, w.mlab, n);
-  hipLaunchKernelGGL((pp_ccl_merge_kernel<false>), dim3(nb), blk, 0, st, (const uint8_t*)w.mask, w.mlab, Ht, W);
-  hipLaunchKernelGGL(pp_ccl_flatten_kernel, dim3(nb), blk, 0, st, w.mlab, n);
-  (void)hipMemsetAsync(w.carea, 0, sizeof(int32_t) * n, st);
-  (void)hipMemsetAsync(w.hasm, 0, n, st);
-  (void)hipMemsetAsync(w.bymax, 0, sizeof(int32_t) * n, st);
-  (void)hipMemsetAsync(w.bxmax, 0, sizeof(int32_t) * n, st);
-  hipLaunchKernelGGL(pp_fill_kernel, dim3(nb), blk, 0, st, w.bymin, 0x7fffffff, n);
-  hipLaunchKernelGGL(pp_fill_kernel, dim3(nb), blk, 0, st, w.bxmin, 0x7fffffff, n);
-  hipLaunchKernelGGL(pp_mcomp_stats_kernel, dim3(nb), blk, 0, st, (const int32_t*)w.mlab, (const int32_t*)w.markers, Ht, W,
-                     w.carea, w.bymin, w.bymax, w.bxmin, w.bxmax, w.hasm);
-  hipLaunchKernelGGL(pp_mcomp_flag_kernel, dim3(nb), blk, 0, st, (const int32_t*)w.mlab, (const uint8_t*)w.hasm, n, w.flag,
-                     w.carea);
-  MSEG_LAUNCH_CHECK();
-  if (pp_exclusive_scan(w.carea, w.hoff, w.bsum, n, nullptr, st)) return MSEG_ELAUNCH;
-  if (pp_exclusive_scan(w.flag, w.scan, w.bsum, n, w.counters + C_NMCOMP, st)) return MSEG_ELAUNCH;
-  hipLaunchKernelGGL(pp_mcomp_list_kernel, dim3(nb), blk, 0, st, (const int32_t*)w.flag, (const int32_t*)w.scan, n, w.clist);
-  hipLaunchKernelGGL((ppb_flood_wave_kernel<PPW_TILE_S>), dim3(256 * 3), dim3(64), 0, st, (const float*)w.tmp,
-                     (const uint8_t*)w.mask, (const int32_t*)w.mlab, (const int32_t*)w.clist, (const int32_t*)w.hoff,
-                     (const int32_t*)w.carea, (const int32_t*)w.bymin, (const int32_t*)w.bymax, (const int32_t*)w.bxmin,
-                     (const int32_t*)w.bxmax, w.hkey, w.hidx, w.scan, w.out, Ht, W, w.counters, fcnt, b.fpx, (int)C_WORK_S,
-                     0LL, (long long)g_ppw_tile_s, g_ppw_tile_s, g_ppw_rows);
-  hipLaunchKernelGGL((ppb_flood_wave_kernel<PPW_TILE_L>), dim3(256), dim3(64), 0, st, (const float*)w.tmp,
-                     (const uint8_t*)w.mask, (const int32_t*)w.mlab, (const int32_t*)w.clist, (const int32_t*)w.hoff,
-                     (const int32_t*)w.carea, (const int32_t*)w.bymin, (const int32_t*)w.bymax, (const int32_t*)w.bxmin,
-                     (const int32_t*)w.bxmax, w.hkey, w.hidx, w.scan, w.out, Ht, W, w.counters, fcnt, b.fpx, (int)C_WORK_L,
-                     (long long)g_ppw_tile_s, 0x7fffffffffffffffLL, g_ppw_tile_l, g_ppw_rows);
-  hipLaunchKernelGGL(ppb_flood_serial_kernel, dim3((unsigned)N), dim3(64), 0, st, (const float*)w.tmp, (const uint8_t*)w.mask,
-                     (const int32_t*)w.markers, w.hkey, w.hidx, w.out, b, fcnt);
-  hipLaunchKernelGGL(ppb_finalize_kernel, dim3(pp_blocks((size_t)H * W), (unsigned)N), blk, 0, st, (const int32_t*)w.out,
-                     labels, b, (const int32_t*)fcnt, n_instances_dev, status_dev);
-  MSEG_LAUNCH_CHECK();
-  return MSEG_OK;
+  PPFrames fr;
+  if (const int rc = pp_open(&w, &fr, ws, ws_bytes, N, H, W)) return rc;
+  if (pp_distance_smooth(w, fr, cell, row_stride, frame_stride, st)) return MSEG_ELAUNCH;
+  return pp_distance_tail(w, fr, border, row_stride, frame_stride, th_cell, th_seed, true, col_major_ids, labels,
+                          n_instances_dev, status_dev, st);
 }

@@ -120,6 +120,23 @@ def test_postproc_group_equals_single_frames_and_oracle(group):
     _check_group(pp, b, c, want)                    # again on the same workspace
 
 
+def test_postproc_group_of_one_equals_single_frame_and_oracle(group):
+    """the group entry with N = 1 and the one-frame entry run the same kernels over two slab layouts (with and without
+    the separator row, counters behind the workspace or inside it): same labels, instance count and status"""
+    from microbeseg_amd.inference import postprocessing as pp
+    c, b, want = group
+    for (col_major, th_cell, th_seed), (oracle, single) in want.items():
+        for i in range(len(CELLS)):
+            labels, n_inst, status = pp.distance_postprocessing_batch_device(b[i:i + 1], c[i:i + 1], th_seed, th_cell,
+                                                                             col_major_ids=col_major)
+            assert labels.shape == (1, H_PP, W_PP) and n_inst.numel() == 1 and status.numel() == 1
+            got = labels[0].cpu().numpy().view(np.uint16)
+            where = f"frame {i}, col_major {col_major}, ths {(th_cell, th_seed)}"
+            assert np.array_equal(got, single[i][0]), f"{where}: {(got != single[i][0]).sum()} px differ from the one-frame call"
+            assert np.array_equal(got, oracle[i]), f"{where}: {(got != oracle[i]).sum()} px differ from the oracle"
+            assert (int(n_inst[0]), int(status[0])) == single[i][1:], where
+
+
 @pytest.mark.parametrize("rows,tile_s,tile_l", [(1, -1, -1), (16, 0, 0), (2, 400, 2000)])
 def test_postproc_group_spill_and_global_probe_paths(group, rows, tile_s, tile_l):
     from microbeseg_amd import _lib
