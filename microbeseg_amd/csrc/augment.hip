@@ -417,7 +417,10 @@ __global__ void aug_noise_normalize_kernel(const float* __restrict__ in, float* 
     float v = in[t];
     const float sigma = frac[s] * stats[3 * s + 1];       // fraction of the image maximum
     if (sigma > 0.f) {
-      const uint32_t k = (uint32_t)t * 2654435761u + seed;
+      // The seed enters through the hash, twice: added beside the pixel index it only moved the offset into one fixed
+      // 2^32-long sequence (seed + 2654435761 gave the field of seed shifted by one pixel).  hash(seed) inside the pixel
+      // hash alone would leave such pairs (hash(s') = hash(s) + 2654435761); the xor outside it breaks them.
+      const uint32_t k = aug_hash((uint32_t)t * 2654435761u + aug_hash(seed)) ^ seed;
       const uint32_t a = aug_hash(k ^ 0x9e3779b9u), b = aug_hash(k + 0x85ebca6bu + (uint32_t)(t >> 32));
       const float u1 = ((float)(a >> 8) + 0.5f) * (1.f / 16777216.f), u2 = ((float)(b >> 8) + 0.5f) * (1.f / 16777216.f);
       const float g = sqrtf(-2.f * __logf(u1)) * __cosf(6.2831853f * u2);

@@ -37,8 +37,8 @@ def rotation_matrix(deg, H, W):
     return (c, s, cx - c * cx - s * cy, -s, c, cy + s * cx - c * cy)
 
 
-def clahe(v, tiles=8, bins=256, gray=16384, clip=0.01):
-    """Zuiderveld's CLAHE with scikit-image's defaults, the variant csrc/augment.hip implements (module docstring there)."""
+def clahe_maps(v, tiles=8, bins=256, gray=16384, clip=0.01):
+    """-> (maps [tiles][tiles][bins] float32, bin of every pixel): the clipped cumulative mapping of every tile"""
     H, W = v.shape
     g = np.clip(np.floor(v * ((gray - 1) / 65535.0) + 0.5), 0, gray - 1).astype(np.int64)
     b = g // (gray // bins)
@@ -73,6 +73,13 @@ def clahe(v, tiles=8, bins=256, gray=16384, clip=0.01):
                 guard += 1
             scale = np.float32(gray - 1) / np.float32(max(npx, 1))
             maps[ty, tx] = np.minimum(np.cumsum(hist.astype(np.float32)) * scale, np.float32(gray - 1))
+    return maps, b
+
+
+def clahe(v, tiles=8, bins=256, gray=16384, clip=0.01):
+    """Zuiderveld's CLAHE with scikit-image's defaults, the variant csrc/augment.hip implements (module docstring there)."""
+    H, W = v.shape
+    maps, b = clahe_maps(v, tiles, bins, gray, clip)
     yy, xx = np.mgrid[0:H, 0:W]
     fy = (yy.astype(np.float32) + 0.5) * tiles / np.float32(H) - 0.5
     fx = (xx.astype(np.float32) + 0.5) * tiles / np.float32(W) - 0.5
