@@ -565,6 +565,26 @@ int mseg_crop_census(const void* mask, int dtype, int H, int W, int y0, int x0, 
                      int64_t* area, void* ws, size_t ws_bytes, void* stream);
 int mseg_crops_overlay(const uint8_t* show, const uint8_t* outlines, uint8_t* rgb, int K, int S, void* stream);
 
+/* ---- device-resident training set (replaces the per-epoch file reads of src/training/training_dataset.py
+ * :40-63 behind TrainWorker.resident) ----------------------------------------------------------------------------------
+ * One batch out of a plane of a training set held in HBM.  src: [n][HW] elements of src_dtype (MSEG_PIX_*);
+ * idx_dev: int32[N], 0 <= idx < n (validated by the caller on the host); dst: [N][HW] of the type dst_mode names.
+ * Repeated indices and N > n are legal, N == 0 is a no-op.  Pairs (any other: MSEG_EINVAL, nothing is launched):
+ *   MSEG_PIX_U16 -> MSEG_GATHER_RAW   uint16, the bits unchanged (DeviceAugment widens them: mseg_aug_u16_to_f32)
+ *   MSEG_PIX_U16 -> MSEG_GATHER_NORM  fp32  2 * (f32(clip(v, lo, hi)) - lo) / (hi - lo) - 1, every operation rounded to
+ *                                     fp32 in this order: the bits of utils.min_max_normalization; hi <= lo: MSEG_EINVAL
+ *   MSEG_PIX_F32 -> MSEG_GATHER_RAW   fp32, the bits unchanged (distance labels)
+ *   MSEG_PIX_U8  -> MSEG_GATHER_I64   int64 (boundary label for the loss)
+ *   MSEG_PIX_U8  -> MSEG_GATHER_F32   fp32, exact (boundary label for DeviceAugment)
+ * lo / hi are used by MSEG_GATHER_NORM only.  Crop offsets are 64-bit.  16-byte accesses for every crop whose source and
+ * destination addresses allow them, element accesses for the others (odd HW).                                           */
+#define MSEG_GATHER_RAW 0
+#define MSEG_GATHER_F32 1
+#define MSEG_GATHER_NORM 2
+#define MSEG_GATHER_I64 3
+int mseg_set_gather(const void* src, int src_dtype, long long n, long long HW, const int32_t* idx_dev, int N, void* dst,
+                    int dst_mode, float lo, float hi, void* stream);
+
 /* ---- misc ---------------------------------------------------------------------------------------------------- */
 int mseg_version(void);
 const char* mseg_strerror(int code);

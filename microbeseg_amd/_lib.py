@@ -17,6 +17,7 @@ EPI_PLAIN, EPI_SCATTER2X2 = 0, 1
 MORDER_LINEAR, MORDER_PARITY = 0, 1
 ST_F32, ST_BF16 = 0, 1      # tensor storage in HBM (MsegSrc.dtype, MsegIgemm.dst_dtype, `st` arguments)
 PIX_U8, PIX_U16, PIX_I32, PIX_F32 = 0, 1, 2, 3      # MSEG_PIX_*: pixel types of raw frames
+GATHER_RAW, GATHER_F32, GATHER_NORM, GATHER_I64 = 0, 1, 2, 3      # MSEG_GATHER_*: dst_mode of mseg_set_gather
 
 
 class MsegLibraryError(RuntimeError):
@@ -172,6 +173,7 @@ SIGNATURES = {
     "mseg_crop_census_workspace_bytes": (_SZ, []),
     "mseg_crop_census": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _SZ, _P]),
     "mseg_crops_overlay": (_I, [_P, _P, _P, _I, _I, _P]),
+    "mseg_set_gather": (_I, [_P, _I, C.c_longlong, C.c_longlong, _P, _I, _P, _I, _F, _F, _P]),
     "mseg_version": (_I, []),
     "mseg_strerror": (C.c_char_p, [_I]),
     "mseg_last_hip_error": (_I, []),

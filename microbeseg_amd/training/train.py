@@ -11,10 +11,11 @@ written from).  The structure is this build's own:
   ``BestCheckpoint``     best-validation bookkeeping: save on strict improvement, count epochs without one
   ``ShardPlan``          which crops a rank sees in a phase (exact ``nn.DataParallel`` scatter for validation)
   ``_Feeder``            host -> HBM + device-side augmentation of one batch
+  ``resident_set``       (opt-in, ``TrainWorker.resident``) the training set read once and kept in HBM; a batch is a gather
   ``TrainWorker``        ties them together, emits the reference's signals / messages
 
 Additive extensions: Qt is optional (``utils.qt_shim``); ``start_training(..., filters=None, max_epochs=None)``;
-``TrainWorker.precision`` ("bf16": BASELINE configs[2]); with ``num_gpus > 1`` under torch.distributed ``batch_size`` is
+``TrainWorker.precision`` ("bf16": BASELINE configs[2]); ``TrainWorker.resident`` (training/resident_set.py); with ``num_gpus > 1`` under torch.distributed ``batch_size`` is
 the GLOBAL batch exactly as under the reference's ``nn.DataParallel`` (each rank takes ``batch_size // world`` crops of
 it), validation runs without duplicated crops on rank 0's BatchNorm statistics, epoch losses are global so that every
 rank takes the same save / early-stop decisions, and rank 0 writes the files.
@@ -350,6 +351,13 @@ class TrainWorker(QObject):
                             # GPU-bound even at batch 4 (bf16 8.0 ms eager with the weight gradients on a second stream,
                             # 8.7-8.8 ms replayed) — the replay buys host time (GUI thread, data loader), not throughput
 
+    resident = False        # True: the crops are read once and stay in HBM, a batch is one gather launch per plane
+                            # (training/resident_set.py) instead of file reads in DataLoader workers + upload.  Same batches,
+                            # same model for a seeded run.  Falls back to the loader route (one text_output line says why)
+                            # on a CPU device, for crops of mixed shapes, over budget, or if the upload does not fit
+    resident_max_bytes = 8 << 30    # budget of the resident set; a quarter of the free device memory also bounds it
+    _resident_state = None          # (key, ResidentSet or None) of the current start_training call
+
     augment_clahe = 'zuiderveld'    # CLAHE branch of the Contrast augmentation: 'library' = scikit-image's routine bit for bit
                                     # (csrc/clahe.hip, what the reference computes), 'zuiderveld' = the earlier stand-in
 
@@ -367,6 +375,17 @@ class TrainWorker(QObject):
     def start_training(self, path_data, path_models, label_type, iterations, optimizer, batch_size, device, num_gpus,
                        print_output=False, filters=None, max_epochs=None):
         """ Train ``iterations`` models on ``path_data/{train,val}`` and store them in ``path_models``. """
+        from .. import engine
+        self._resident_state = None
+        try:
+            self._start_training(path_data, path_models, label_type, iterations, optimizer, batch_size, device, num_gpus,
+                                 print_output, filters, max_epochs)
+        finally:
+            self._release_resident()
+        self.finished.emit()
+
+    def _start_training(self, path_data, path_models, label_type, iterations, optimizer, batch_size, device, num_gpus,
+                        print_output, filters, max_epochs):
         from .. import engine
         with engine.precision_scope(self.precision):
             n_masks = {split: len(list((path_data / split).glob('mask*'))) for split in PHASES} \
@@ -390,7 +409,6 @@ class TrainWorker(QObject):
                     self.progress.emit(100)
             else:
                 self.progress.emit(0)
-        self.finished.emit()
 
     def _train_one_model(self, path_data, path_models, label_type, optimizer, run_name, device, num_gpus, ladder, where,
                          max_epochs, print_output):
@@ -465,6 +483,42 @@ class TrainWorker(QObject):
                     _zip_trainset(path_data, path_models / '{}_trainset.zip'.format(run_name))
             return
 
+    # -- the device-resident training set (opt-in) -------------------------------------------------------------------------
+    def _release_resident(self):
+        state, self._resident_state = self._resident_state, None
+        if state is not None and state[1] is not None:
+            state[1].release()
+            if torch.cuda.is_available():
+                torch.cuda.empty_cache()
+
+    def _resident_set(self, datasets, configs, device):
+        """the ResidentSet of this training request (loaded on first use, then shared by every iteration, the Ranger second
+        run and the retries of the MemoryLadder), or None: the loader route.  The reason for None is said once."""
+        if not self.resident:
+            return None
+        train = datasets['train']
+        raw = bool(getattr(train.transform, 'device_augment', False))
+        key = (str(train.root_dir), configs['label_type'], str(device), raw)
+        if self._resident_state is not None and self._resident_state[0] == key:
+            return self._resident_state[1]
+        self._release_resident()
+        from . import resident_set as R
+        rset = None
+        try:
+            if device.type != 'cuda':
+                raise R.ResidentUnavailable('the device is not a GPU')
+            host = R.load_host(train.root_dir, configs['label_type'], pin=True)
+            need, free = R.host_bytes(host), torch.cuda.mem_get_info(device)[0]
+            if not R.resident_fits(need, self.resident_max_bytes, free):
+                raise R.ResidentUnavailable('{} bytes exceed the budget (resident_max_bytes {}, a quarter of the free '
+                                            'device memory {})'.format(need, self.resident_max_bytes, free // 4))
+            t = datasets['val'].transform
+            rset = R.ResidentSet(host, configs['label_type'], device, t.min_value, t.max_value, raw_train=raw)
+        except R.ResidentUnavailable as why:
+            self.text_output.emit('Resident training set not used ({}): reading crops with the data loader'.format(why))
+        self._resident_state = (key, rset)
+        return rset
+
     # -- one optimisation run ----------------------------------------------------------------------------------------------
     def _loaders(self, datasets, configs, device, world, rank):
         if self.num_workers is not None:
@@ -477,6 +531,11 @@ class TrainWorker(QObject):
             except (AttributeError, NotImplementedError):
                 workers = 4
         plans = {x: ShardPlan(len(datasets[x]), configs['batch_size'], world, rank, shuffle=(x == 'train')) for x in PHASES}
+        rset = self._resident_set(datasets, configs, device)
+        if rset is not None:                        # additive key, as 'precision': the loader route's .json has none
+            configs['data_route'] = 'resident'
+            from .resident_set import ResidentBatches
+            return plans, {x: ResidentBatches(rset, x, plans[x], training=(x == 'train')) for x in PHASES}
         loaders = {x: torch.utils.data.DataLoader(datasets[x], batch_sampler=plans[x], pin_memory=True,
                                                   worker_init_fn=seed_worker, num_workers=workers) for x in PHASES}
         return plans, loaders

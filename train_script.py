@@ -5,7 +5,7 @@ Same flags as the reference ``train_script.py`` (:16-28): ``--omero_id/-id``, ``
 ``--iterations/-i`` (1), ``--method/-m`` (distance), ``--optimizer/-o`` (Ranger), ``--model_path/-r``,
 ``--device/-d`` (cuda:0), OMERO credentials.  Extensions: ``--train_path`` (a local, already exported + labelled
 training set ``<path>/{train,val}/{img,mask,cell_dist,neighbor_dist|boundary}_*.tif``),
-``--filters F0 F1``, ``--max_epochs`` and ``--augment_clahe {zuiderveld,library}`` (``library``: the CLAHE branch of the
+``--filters F0 F1``, ``--max_epochs``, ``--resident`` (the training set stays in device memory) and ``--augment_clahe {zuiderveld,library}`` (``library``: the CLAHE branch of the
 Contrast augmentation computes exactly what the reference's scikit-image call does).  Exporting a set from OMERO and creating the training labels
 (reference train_script.py:41-114) are outside the hot path and need the reference's OMERO stack.
 Multi-GPU: ``python -m torch.distributed.run --nproc-per-node N train_script.py ...`` (one process per GPU, RCCL).
@@ -39,6 +39,9 @@ def main():
                         help='[extension] CLAHE branch of the Contrast augmentation: library = scikit-image\'s '
                              'equalize_adapthist(clip_limit=0.01) bit for bit, as the reference computes it; zuiderveld = '
                              'the textbook form this build used so far (the default for now)')
+    parser.add_argument('--resident', action='store_true',
+                        help='[extension] read the training set once and keep it in device memory; every batch is then '
+                             'gathered on the device (same batches, same model for a seeded run)')
     args = parser.parse_args()
 
     if args.method not in ('boundary', 'distance'):
@@ -70,6 +73,7 @@ def main():
     worker = TrainWorker()
     worker.precision = args.precision
     worker.augment_clahe = args.augment_clahe
+    worker.resident = args.resident
     worker.start_training(path_data, model_path, args.method, args.iterations, args.optimizer.lower(), args.batch_size,
                           device, world, True, filters=args.filters, max_epochs=args.max_epochs)
     if world > 1:
