@@ -182,7 +182,7 @@ int mseg_first_conv_fwd(const float* x4, const float* w, const float* bias, int 
  *                            first layer does not take the kernel above                                                   */
 #define MSEG_PIX_U8 0
 #define MSEG_PIX_U16 1
-#define MSEG_PIX_I32 2 /* mseg_stack_relabel only */
+#define MSEG_PIX_I32 2 /* label stacks: mseg_stack_relabel, mseg_cell_measure, mseg_cell_links */
 #define MSEG_PIX_F32 3 /* mseg_clahe_u16 only: fp32 holding the integers 0..65535 */
 int mseg_frame_minmax(const void* raw, int dtype, size_t npix, uint32_t* minmax, void* stream);
 int mseg_first_conv_fwd_raw(const void* raw, int dtype, int H0, int W0, int pad_top, int pad_left, const uint32_t* minmax,
@@ -536,6 +536,37 @@ int mseg_region_stats(const int32_t* labels, int T, int H, int W, const int64_t*
 size_t mseg_overlay_workspace_bytes(void);
 int mseg_overlay_rgb(const void* img, int dtype, int T, int H, int W, int C, const uint8_t* outlines, uint8_t* out,
                      void* ws, size_t ws_bytes, void* stream);
+
+/* ---- per-cell table of a segmented stack (csrc/cells.hip) — an extension, the reference has no such table --
+ * labels: uint16 (MSEG_PIX_U16) or int32 (MSEG_PIX_I32) [T][H][W]; label_off: int64 [T + 1] on the device as in
+ * mseg_region_stats: cell l of frame t has slot label_off[t] + l - 1, label_off[T] = n_labels; ids beyond a frame's table
+ * (and negative ones) are ignored, ids that are absent keep area 0.  H * W < 2^31 - 512.
+ * mseg_cell_measure: img is the intensity image, uint8 (MSEG_PIX_U8) or uint16 (MSEG_PIX_U16), read in place: element
+ *   (t, ch, y, x) lies at t * frame_stride + ch * chan_stride + y * row_stride + x * pix_stride, in elements ([T,C,H,W],
+ *   [T,H,W], [H,W,3] and [3,H,W] sources without a copy).  C == 0 or img == NULL: shape only, no channel buffer is touched.
+ *   Outputs (all integers, written whole by the call, exact and independent of summation order):
+ *     shape      uint64 [6][n_labels]     area, sum_y, sum_x, sum_yy, sum_xx, sum_xy of the cell's pixel coordinates
+ *     bbox       int32  [n_labels][4]     min_row, min_col, max_row + 1, max_col + 1 (scikit-image's half-open box)
+ *     ch_sums    uint64 [2][C][n_labels]  sum and sum of squares of the cell's pixel values per channel
+ *     ch_minmax  uint32 [2][C][n_labels]  min and max
+ *     bg_sums    uint64 [3][T][C]         count, sum and sum of squares over the background (label 0) of a frame
+ *     bg_minmax  uint32 [2][T][C]         its min and max
+ *   An absent cell has zeros everywhere (bbox and min included), and so has a frame without background pixels.
+ * mseg_cell_links: for every frame t >= 1 and cell l of it, pred[slot] = the label m of frame t - 1 (1 <= m <= K_{t-1})
+ *   that shares the most pixels (same y, x) with l, ties to the smallest m, 0 where nothing overlaps; overlap[slot] = that
+ *   pixel count; frame 0 gets zeros.  The (l, m) pairs of a frame pair are counted in an open-addressing table of
+ *   table_cap entries (a power of two, 64 <= table_cap <= 2^31; a table of more than H * W entries cannot fill up);
+ *   status: int32 [T] on the device, status[t] != 0: the table of the pair (t - 1, t) was full, pred / overlap of frame t
+ *   are then NOT valid and the pair has to be redone with a larger table.  ws >= mseg_cell_links_workspace_bytes (12 bytes
+ *   per table entry and frame pair + 8 per cell; 0 = bad arguments).                                                     */
+int mseg_cell_measure(const void* labels, int label_dtype, int T, int H, int W, const int64_t* label_off, int64_t n_labels,
+                      const void* img, int img_dtype, int C, int64_t frame_stride, int64_t chan_stride, int64_t row_stride,
+                      int64_t pix_stride, uint64_t* shape, int32_t* bbox, uint64_t* ch_sums, uint32_t* ch_minmax,
+                      uint64_t* bg_sums, uint32_t* bg_minmax, void* stream);
+size_t mseg_cell_links_workspace_bytes(int T, int64_t n_labels, int64_t table_cap);
+int mseg_cell_links(const void* labels, int dtype, int T, int H, int W, const int64_t* label_off, int64_t n_labels,
+                    int64_t table_cap, int32_t* pred, int32_t* overlap, int32_t* status, void* ws, size_t ws_bytes,
+                    void* stream);
 
 /* ---- training-set preparation (DataCropWorker src/utils/data_cropping.py:157-264,286,
  * DataImportWorker src/utils/data_import.py:125-194, DataExportWorker src/utils/data_export.py:100-101) -----------------

@@ -6,7 +6,8 @@ Same flags and output as the reference ``infer_script_local.py`` (:17-25, :164-1
 ``--overwrite/-o``; writes ``mask_<stem>_channel<c>.tif`` (uint16, [T, H, W] squeezed); ``--export`` adds the files of
 the GUI's Export button (inference/result_export.py) for the segmented channel of uint8 / uint16 stacks;
 ``--frame_batch N`` sends the frames of a stack through the network and the post-processing in groups of N;
-``--clahe`` enhances every uint8 / uint16 frame first, like the reference's ``ContrastEnhancement(apply_clahe=True)``.
+``--clahe`` enhances every uint8 / uint16 frame first, like the reference's ``ContrastEnhancement(apply_clahe=True)``;
+``--cells`` adds ``mask_<stem>_channel<c>_cells.csv``, one row per cell and frame (inference/cells.py).
 """
 import argparse
 from pathlib import Path
@@ -33,7 +34,33 @@ def select_frames(img, channel, name):
     raise Exception('Adapt script for your data format!')
 
 
-def main():
+def select_channels(img, channels, name):
+    """The sibling of select_frames for the cell table: the ``channels`` of the source image as a [T, C, H, W] VIEW
+    (strides, no copy) whose frames are those select_frames returns.  Sources without a channel axis ([H, W], [T, H, W])
+    have the single channel 0.  A channel the image does not have raises ValueError; None = unsupported shape."""
+    if img.ndim == 2:
+        view = img[None, None]
+    elif img.ndim == 3:
+        if img.shape[-1] == 3:
+            view = np.moveaxis(img, -1, 0)[None]
+        elif img.shape[0] == 3:
+            view = img[None]
+        else:
+            view = img[:, None]
+    elif img.ndim == 4:
+        view = img
+    else:
+        return None
+    missing = [c for c in channels if c < 0 or c >= view.shape[1]]
+    if missing:
+        raise ValueError(f'{name}: channel(s) {missing} requested for the cell table, the image has {view.shape[1]}')
+    step = channels[1] - channels[0] if len(channels) > 1 else 1
+    if step > 0 and all(b - a == step for a, b in zip(channels, channels[1:])):
+        return view[:, channels[0]:channels[-1] + 1:step]           # basic slicing: still a view
+    return view[:, list(channels)]
+
+
+def build_parser():
     parser = argparse.ArgumentParser(description='microbeSEG inference on local files (MI355X-native hot path)')
     parser.add_argument('--img_dir', '-i', required=True, type=str, help='Directory with .tif images / stacks')
     parser.add_argument('--model', '-m', required=True, type=str, help='Model to use (path without suffix)')
@@ -67,7 +94,31 @@ def main():
                              '<result_path>/<image stem>_channel<c>_export/.  The exported image and overlay hold the '
                              'segmented channel only (the GUI exports every channel); uint8 / uint16 images only, other '
                              'stacks are segmented but not exported')
-    args = parser.parse_args()
+    parser.add_argument('--cells', default=False, action='store_true',
+                        help='[extension] also write <mask file stem>_cells.csv: one row per cell and frame with area, '
+                             'centroid, bounding box, axis lengths, orientation, the intensity of the measured channels '
+                             '(mean, std, min, max, sum, background mean) and pred_label / overlap / track_id / '
+                             'parent_track.  Tracks come from OVERLAP linking (a cell follows the cell of the previous '
+                             'frame it shares the most pixels with): there is no motion model and no gap closing')
+    parser.add_argument('--measure_channels', default=None, nargs='+', type=int,
+                        help='[extension] with --cells: channels of the source image to measure (default: the segmented '
+                             'channel; images without a channel axis have channel 0).  uint8 / uint16 images only: other '
+                             'images get the shape and link columns.  A channel an image does not have is an error')
+    parser.add_argument('--min_overlap', default=1, type=int,
+                        help='[extension] with --cells: links that share fewer pixels are dropped before tracks are built')
+    return parser
+
+
+def measured_channels(args, img):
+    """channels of ``img`` that --cells measures: --measure_channels, else the segmented channel (0 without channel axis)"""
+    if args.measure_channels is not None:
+        return list(args.measure_channels)
+    has_axis = img.ndim == 4 or (img.ndim == 3 and 3 in (img.shape[0], img.shape[-1]))
+    return [args.channel if has_axis else 0]
+
+
+def main():
+    args = build_parser().parse_args()
 
     imgs_path = Path(args.img_dir)
     result_path = (Path(__file__).parent / 'results') if args.result_path is None else Path(args.result_path)
@@ -84,17 +135,24 @@ def main():
     if len(file_ids) == 0:
         print('No files found')
         return
+    if args.cells:                      # a channel an image does not have stops the run before any inference
+        for img_id in file_ids:
+            img = tiff.imread(str(img_id))
+            select_channels(img, measured_channels(args, img), img_id.name)
+        del img
     worker = InferWorker(model=args.model, device=args.device, ths=args.thresholds, channel=args.channel,
                          sliding_window=args.sliding_window)
     worker.precision = args.precision
     worker.frame_batch = args.frame_batch
     worker.apply_clahe = args.clahe
+    worker.min_overlap = args.min_overlap
     worker.text_output.connect(print)
     torch.set_grad_enabled(False)
     print('--- Start inference ---')
     for img_id in file_ids:
         out_file = result_path / f"mask_{img_id.stem}_channel{args.channel}.tif"
-        frames = select_frames(tiff.imread(str(img_id)), args.channel, img_id.name)
+        img = tiff.imread(str(img_id))
+        frames = select_frames(img, args.channel, img_id.name)
         if frames is None:
             continue
         if out_file.is_file() and not args.overwrite:
@@ -116,6 +174,14 @@ def main():
         if export:
             from microbeseg_amd.inference.result_export import export_local
             export_local(frames, rois, result_path / f"{img_id.stem}_channel{args.channel}_export", img_id.name)
+        if args.cells:
+            from microbeseg_amd.inference.cells import write_cells
+            channels = measured_channels(args, img)
+            view = select_channels(img, channels, img_id.name)
+            if view.dtype not in (np.uint8, np.uint16):
+                print(f'Skip intensity columns of {img_id.stem} (they need uint8 / uint16 images, got {view.dtype})')
+                view, channels = None, []
+            write_cells(worker.cell_table(results, view, channels), out_file.with_name(out_file.stem + '_cells.csv'))
     print('--- Finished ---')
 
 

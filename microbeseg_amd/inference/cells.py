@@ -1,0 +1,339 @@
+""" The per-cell table of a segmented stack: shape, intensity in the image's channels, and overlap links between frames.
+
+[extension] The reference stops at the per-frame means of its Analysis worker (src/inference/analysis.py:151-170); the
+per-cell values behind those means are what people who follow single microbes need.  The integer sums come from the
+device (csrc/cells.hip: ``mseg_cell_measure``, ``mseg_cell_links``), every float of the table is derived
+from them here on the host in Python integers and fp64, so the table is exact where it can be and identical from run to
+run.  ``assemble_tracks`` turns the links into track ids: this is OVERLAP linking — a cell follows the cell of the
+previous frame it shares the most pixels with.  There is no motion model and no gap closing: a cell that moves further
+than its own extent between two frames, or that is missed in one frame, starts a new track.
+"""
+import ctypes as C
+import math
+
+import numpy as np
+import pandas as pd
+import torch
+
+from .. import _lib
+
+SHAPE_COLUMNS = ['frame', 'label', 'area', 'centroid_y', 'centroid_x', 'bbox_min_row', 'bbox_min_col', 'bbox_max_row',
+                 'bbox_max_col', 'major_axis_length', 'minor_axis_length', 'orientation', 'touches_border']
+CHANNEL_COLUMNS = ['mean_ch{c}', 'std_ch{c}', 'min_ch{c}', 'max_ch{c}', 'sum_ch{c}', 'bg_mean_ch{c}']
+LINK_COLUMNS = ['pred_label', 'overlap', 'track_id', 'parent_track']
+MIN_TABLE = 64        # smallest pair table mseg_cell_links accepts
+
+
+def columns(channels=(), link=True):
+    """the table's columns, in order, for the measured ``channels``"""
+    cols = list(SHAPE_COLUMNS)
+    for c in channels:
+        cols += [name.format(c=int(c)) for name in CHANNEL_COLUMNS]
+    return cols + (list(LINK_COLUMNS) if link else [])
+
+
+def _device(device=None):
+    if device is not None:
+        return torch.device(device)
+    if not torch.cuda.is_available():
+        raise RuntimeError("No MI355X visible: the cell table is measured on the device (there is no CPU path)")
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def _stream(dev):
+    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def _labels_to_device(mask, dev):
+    """host array or device tensor -> (contiguous [T, H, W] device tensor: int16 holding uint16 bits, or int32; MSEG_PIX_*)"""
+    if isinstance(mask, torch.Tensor):
+        lab = mask if mask.dim() == 3 else mask[None]
+        if lab.dtype not in (torch.int16, torch.int32):
+            if lab.dtype in (torch.uint8, torch.int64, getattr(torch, "uint16", torch.int16)):
+                lab = lab.to(torch.int32)
+            else:
+                raise ValueError(f"label tensors are int16 (uint16 bits), int32, uint8 or int64, got {lab.dtype}")
+        lab = lab.to(dev).contiguous()
+    else:
+        m = np.asarray(mask)
+        if m.ndim == 2:
+            m = m[None]
+        if m.ndim != 3 or m.dtype.kind not in "iu":
+            raise ValueError("mask: an integer [T, H, W] or [H, W] label array expected")
+        if m.dtype == np.uint16:
+            lab = torch.from_numpy(np.ascontiguousarray(m).view(np.int16)).to(dev)
+        else:
+            if m.min(initial=0) < 0 or m.max(initial=0) > 2 ** 31 - 1:
+                raise ValueError("label values must lie in 0 .. 2^31 - 1")
+            lab = torch.from_numpy(np.ascontiguousarray(m.astype(np.int32))).to(dev)
+    return lab, (_lib.PIX_U16 if lab.dtype == torch.int16 else _lib.PIX_I32)
+
+
+def _frame_counts(lab):
+    """largest id of every frame = the size of its table"""
+    T = lab.shape[0]
+    k = np.zeros(T, np.int64)
+    for t in range(T):                       # per frame: the widened copy of a uint16 frame stays one frame large
+        f = lab[t]
+        k[t] = int((f.to(torch.int32) & 0xFFFF).max()) if f.dtype == torch.int16 else max(int(f.max()), 0)
+    return k
+
+
+def _image_to_device(img, lab_shape, dev):
+    """-> (device tensor that owns the memory, MSEG_PIX_*, n_channels, element strides (frame, channel, row, pixel)) of an
+    image given as [T, C, H, W] or [T, H, W] ([H, W] for a single frame), with ANY strides: a view of an [H, W, 3] or
+    [3, H, W] source is measured in place.  None for dtypes other than uint8 / uint16."""
+    T, H, W = lab_shape
+    if isinstance(img, torch.Tensor):
+        if img.dtype not in (torch.uint8, torch.int16, getattr(torch, "uint16", torch.int16)):
+            return None
+        t = img.to(dev)
+        if t.dim() == 2:
+            t = t[None]
+        if t.dim() == 3:
+            t = t[:, None]
+        if tuple(t.shape[0:1] + t.shape[2:]) != (T, H, W):
+            raise ValueError(f"image {tuple(t.shape)} does not match the label stack {(T, H, W)}")
+        pix = _lib.PIX_U8 if t.dtype == torch.uint8 else _lib.PIX_U16
+        return t, t.data_ptr(), pix, t.shape[1], tuple(int(s) for s in t.stride())
+    a = np.asarray(img)
+    if a.dtype not in (np.uint8, np.uint16):
+        return None
+    if a.ndim == 2:
+        a = a[None]
+    if a.ndim == 3:
+        a = a[:, None]
+    if a.ndim != 4 or (a.shape[0],) + a.shape[2:] != (T, H, W):
+        raise ValueError(f"image {a.shape} does not match the label stack {(T, H, W)}")
+    item = a.dtype.itemsize
+    if any(s < 0 or s % item for s in a.strides):
+        a = np.ascontiguousarray(a)
+    strides = tuple(s // item for s in a.strides)
+    span = 1 + sum((n - 1) * s for n, s in zip(a.shape, strides))
+    flat = np.lib.stride_tricks.as_strided(a, shape=(span,), strides=(item,))   # the memory the view spans
+    host = flat.view(np.int16) if a.dtype == np.uint16 else flat
+    t = torch.from_numpy(np.ascontiguousarray(host)).to(dev)
+    return t, t.data_ptr(), (_lib.PIX_U8 if a.dtype == np.uint8 else _lib.PIX_U16), a.shape[1], strides
+
+
+def _channel_groups(channels):
+    """channel indices -> runs (first, step, count) that one call covers with a single channel stride"""
+    groups, i = [], 0
+    while i < len(channels):
+        if i + 1 == len(channels):
+            groups.append((channels[i], 1, 1))
+            break
+        step, j = channels[i + 1] - channels[i], i + 1
+        while j + 1 < len(channels) and channels[j + 1] - channels[j] == step:
+            j += 1
+        groups.append((channels[i], step, j - i + 1))
+        i = j + 1
+    return groups
+
+
+def measure_raw(lab, pix, off, image=None, channels=()):
+    """The integer sums of ``mseg_cell_measure`` as host arrays.  lab: device labels [T, H, W]; off: int64 [T + 1] host
+    table; image: the tuple of ``_image_to_device``.  -> dict: shape uint64 [6, n], bbox int32 [n, 4], ch_sums uint64
+    [2, C, n], ch_minmax uint32 [2, C, n], bg_sums uint64 [3, T, C], bg_minmax uint32 [2, T, C]"""
+    lib = _lib.load()
+    dev = lab.device
+    T, H, W = (int(v) for v in lab.shape)
+    n = int(off[-1])
+    off_d = torch.from_numpy(np.ascontiguousarray(off, np.int64)).to(dev)
+    shape = torch.zeros((6, max(n, 1)), dtype=torch.int64, device=dev)
+    bbox = torch.zeros((max(n, 1), 4), dtype=torch.int32, device=dev)
+    out = {"ch_sums": [], "ch_minmax": [], "bg_sums": [], "bg_minmax": []}
+    calls = _channel_groups(list(channels)) if image is not None and len(channels) else [None]
+    for g in calls:
+        if g is None:
+            ptr, ipix, Cg, fs, cs, rs, ps = None, 0, 0, 0, 0, 0, 0
+        else:
+            _, base, ipix, _, (fs, cs0, rs, ps) = image
+            first, step, Cg = g
+            ptr, cs = base + first * cs0 * (1 if ipix == _lib.PIX_U8 else 2), step * cs0
+        chs = torch.zeros((2, max(Cg, 1), max(n, 1)), dtype=torch.int64, device=dev)
+        chm = torch.zeros((2, max(Cg, 1), max(n, 1)), dtype=torch.int32, device=dev)
+        bgs = torch.zeros((3, T, max(Cg, 1)), dtype=torch.int64, device=dev)
+        bgm = torch.zeros((2, T, max(Cg, 1)), dtype=torch.int32, device=dev)
+        _lib.check(lib.mseg_cell_measure(lab.data_ptr(), pix, T, H, W, off_d.data_ptr(), n, ptr, ipix, Cg, fs, cs, rs, ps,
+                                         shape.data_ptr(), bbox.data_ptr(), chs.data_ptr(), chm.data_ptr(),
+                                         bgs.data_ptr(), bgm.data_ptr(), _stream(dev)), "cell_measure")
+        if Cg:
+            out["ch_sums"].append(chs.cpu().numpy().view(np.uint64)[:, :, :n])
+            out["ch_minmax"].append(chm.cpu().numpy().view(np.uint32)[:, :, :n])
+            out["bg_sums"].append(bgs.cpu().numpy().view(np.uint64))
+            out["bg_minmax"].append(bgm.cpu().numpy().view(np.uint32))
+    res = {"shape": shape.cpu().numpy().view(np.uint64)[:, :n], "bbox": bbox.cpu().numpy()[:n]}
+    empty = {"ch_sums": np.zeros((2, 0, n), np.uint64), "ch_minmax": np.zeros((2, 0, n), np.uint32),
+             "bg_sums": np.zeros((3, T, 0), np.uint64), "bg_minmax": np.zeros((2, T, 0), np.uint32)}
+    for key, parts in out.items():
+        res[key] = np.concatenate(parts, axis=2 if key.startswith("bg") else 1) if parts else empty[key]
+    return res
+
+
+def _pow2(v):
+    return 1 << max(int(v) - 1, 0).bit_length()
+
+
+def _links_call(lab, pix, off, cap):
+    lib = _lib.load()
+    dev = lab.device
+    T, H, W = (int(v) for v in lab.shape)
+    n = int(off[-1])
+    off_d = torch.from_numpy(np.ascontiguousarray(off, np.int64)).to(dev)
+    pred = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+    ovl = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+    status = torch.zeros(T, dtype=torch.int32, device=dev)
+    nbytes = lib.mseg_cell_links_workspace_bytes(T, n, cap)
+    if nbytes == 0:
+        raise ValueError(f"mseg_cell_links: no workspace for T = {T}, {n} cells, table {cap}")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    _lib.check(lib.mseg_cell_links(lab.data_ptr(), pix, T, H, W, off_d.data_ptr(), n, cap, pred.data_ptr(), ovl.data_ptr(),
+                                   status.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)), "cell_links")
+    return pred.cpu().numpy()[:n], ovl.cpu().numpy()[:n], status.cpu().numpy()
+
+
+def link_raw(lab, pix, off, table_cap=None):
+    """``mseg_cell_links`` for the whole stack -> (pred int32 [n], overlap int32 [n]) on the host.  The pair tables start
+    at 4 entries per cell of the two frames; a frame pair whose table filled up (the device status word says so) is redone
+    on its own with a table of more than H * W entries, which cannot fill up: the result is always exact."""
+    T, H, W = (int(v) for v in lab.shape)
+    k = np.diff(off)
+    if table_cap is None:
+        pair = int((k[1:] + k[:-1]).max()) if T > 1 else 0
+        table_cap = min(max(MIN_TABLE, _pow2(4 * pair)), _pow2(H * W + 1))
+    pred, ovl, status = _links_call(lab, pix, off, int(table_cap))
+    pred, ovl = pred.copy(), ovl.copy()
+    for t in np.nonzero(status)[0]:
+        sub = np.asarray(off[t - 1:t + 2], np.int64) - off[t - 1]
+        p2, o2, s2 = _links_call(lab[t - 1:t + 1], pix, sub, max(MIN_TABLE, _pow2(H * W + 1)))
+        if s2.any():
+            raise RuntimeError("mseg_cell_links: a table of more than H * W entries reported full")
+        pred[off[t]:off[t + 1]] = p2[sub[1]:]
+        ovl[off[t]:off[t + 1]] = o2[sub[1]:]
+    return pred, ovl
+
+
+def assemble_tracks(frame, label, pred, overlap, min_overlap=1):
+    """ Track ids from overlap links; pure host code, O(cells).
+
+    ``frame``, ``label``, ``pred``, ``overlap``: one entry per cell, in (frame, label) order; ``pred`` names a label of the
+    previous frame (0 = none).  Links with ``overlap < min_overlap`` are dropped.  With n_succ(m) = the number of cells that
+    name m: a cell whose predecessor has exactly one successor inherits its track_id and parent_track; a cell whose
+    predecessor has two or more successors starts a new track whose parent_track is the predecessor's track (a division);
+    a cell without predecessor starts a new track with parent_track 0.  Track ids count from 1 in order of first
+    appearance.  A cell that loses a merge has no successor: its track ends.
+
+    Overlap linking only: no motion model, no gap closing.
+    :return: (track_id int64 [n], parent_track int64 [n])
+    """
+    frame, label = np.asarray(frame, np.int64), np.asarray(label, np.int64)
+    pred = np.where(np.asarray(overlap, np.int64) >= int(min_overlap), np.asarray(pred, np.int64), 0)
+    index = {(int(f), int(l)): i for i, (f, l) in enumerate(zip(frame, label))}
+    src = np.full(len(frame), -1, np.int64)
+    for i, (f, p) in enumerate(zip(frame, pred)):
+        if p > 0:
+            src[i] = index.get((int(f) - 1, int(p)), -1)
+    n_succ = np.bincount(src[src >= 0], minlength=len(frame))
+    track, parent = np.zeros(len(frame), np.int64), np.zeros(len(frame), np.int64)
+    nxt = 1
+    for i in range(len(frame)):
+        j = src[i]
+        if j >= 0 and n_succ[j] == 1:
+            track[i], parent[i] = track[j], parent[j]
+            continue
+        track[i], nxt = nxt, nxt + 1
+        parent[i] = track[j] if j >= 0 else 0
+    return track, parent
+
+
+def _axes(n, sy, sx, syy, sxx, sxy):
+    """(major, minor, orientation) of one cell from its exact sums: the formulas of rs_axes_kernel (csrc/analysis.hip) and
+    the orientation of scikit-image 0.18.3 regionprops, whose inertia tensor is [[var_x, -cov], [-cov, var_y]]:
+    0.5 * atan2(-2 b, c - a) with a = var_x, b = -cov, c = var_y, and +-pi/4 by the sign of b where a == c."""
+    nn = float(n) * float(n)
+    vy = float(n * syy - sy * sy) / nn
+    vx = float(n * sxx - sx * sx) / nn
+    cov = float(n * sxy - sx * sy) / nn
+    h, q = 0.5 * (vy + vx), math.sqrt(0.25 * (vy - vx) * (vy - vx) + cov * cov)
+    major, minor = 4.0 * math.sqrt(max(h + q, 0.0)), 4.0 * math.sqrt(max(h - q, 0.0))
+    a, b, c = vx, -cov, vy
+    if a - c == 0:
+        orientation = -math.pi / 4.0 if b < 0 else math.pi / 4.0
+    else:
+        orientation = 0.5 * math.atan2(-2.0 * b, c - a)
+    return major, minor, orientation
+
+
+def table_from_sums(off, H, W, raw, channels=(), links=None, min_overlap=1):
+    """the DataFrame from the integer sums of ``measure_raw`` (and ``links`` = (pred, overlap) or None); host arithmetic in
+    Python integers and fp64"""
+    off = np.asarray(off, np.int64)
+    area = raw["shape"][0]
+    rows = {c: [] for c in columns(channels, links is not None)}
+    sh = [[int(v) for v in plane] for plane in raw["shape"]]
+    for t in range(len(off) - 1):
+        bg = []
+        for ci in range(len(channels)):
+            cnt = int(raw["bg_sums"][0, t, ci])
+            bg.append(int(raw["bg_sums"][1, t, ci]) / cnt if cnt else float("nan"))
+        for s in range(int(off[t]), int(off[t + 1])):
+            n = sh[0][s]
+            if n == 0:
+                continue
+            major, minor, orientation = _axes(n, sh[1][s], sh[2][s], sh[3][s], sh[4][s], sh[5][s])
+            r0, c0, r1, c1 = (int(v) for v in raw["bbox"][s])
+            vals = [t, s - int(off[t]) + 1, n, sh[1][s] / n, sh[2][s] / n, r0, c0, r1, c1, major, minor, orientation,
+                    bool(r0 == 0 or c0 == 0 or r1 == H or c1 == W)]
+            for ci in range(len(channels)):
+                sv, sq = int(raw["ch_sums"][0, ci, s]), int(raw["ch_sums"][1, ci, s])
+                vals += [sv / n, math.sqrt((n * sq - sv * sv) / (n * n)), int(raw["ch_minmax"][0, ci, s]),
+                         int(raw["ch_minmax"][1, ci, s]), sv, bg[ci]]
+            if links is not None:
+                vals += [int(links[0][s]), int(links[1][s]), 0, 0]
+            for c, v in zip(rows, vals):
+                rows[c].append(v)
+    df = pd.DataFrame(rows, columns=list(rows))
+    assert int((area > 0).sum()) == len(df)
+    if links is not None:
+        df["track_id"], df["parent_track"] = assemble_tracks(df["frame"], df["label"], df["pred_label"], df["overlap"],
+                                                             min_overlap)
+    return df
+
+
+def measure_cells(mask, img=None, channels=None, link=True, min_overlap=1, device=None):
+    """ One row per cell of a segmented stack, ordered by (frame, label).
+
+    :param mask: label stack [T, H, W] (or one frame [H, W]): host array or device tensor (int16 holding uint16 bits, or
+        int32); 0 is background, a frame's cells are its ids 1 .. max.
+    :param img: intensity image, uint8 / uint16, as [T, C, H, W], [T, H, W] or [H, W] with any strides (host array or
+        device tensor; read in place), or None for the shape and link columns only.
+    :param channels: indices into the channel axis of ``img`` to measure (default: all); they name the columns.
+    :param link: add pred_label / overlap (the label of the previous frame sharing the most pixels, ties to the smaller
+        label, 0 = none) and track_id / parent_track (``assemble_tracks``).  Overlap linking: no motion model, no gap closing.
+    :param min_overlap: links with fewer shared pixels are dropped before the tracks are assembled.
+    :return: pandas.DataFrame with the columns of ``columns(channels, link)``.
+    """
+    dev = _device(device)
+    with torch.cuda.device(dev):
+        lab, pix = _labels_to_device(mask, dev)
+        T, H, W = (int(v) for v in lab.shape)
+        off = np.zeros(T + 1, np.int64)
+        np.cumsum(_frame_counts(lab), out=off[1:])
+        image = None
+        if img is not None:
+            image = _image_to_device(img, (T, H, W), dev)
+            if image is None:
+                raise ValueError("only uint8 / uint16 images are measured")
+            channels = list(range(image[3])) if channels is None else [int(c) for c in channels]
+            if any(c < 0 or c >= image[3] for c in channels):
+                raise ValueError(f"channels {channels} requested, the image has {image[3]}")
+        else:
+            channels = []
+        raw = measure_raw(lab, pix, off, image, channels)
+        links = link_raw(lab, pix, off) if link else None
+    return table_from_sums(off, H, W, raw, channels, links, min_overlap)
+
+
+def write_cells(df, csv_path):
+    df.to_csv(csv_path, index=False)

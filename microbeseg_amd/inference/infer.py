@@ -91,6 +91,8 @@ class InferWorker(QObject):
     # [extension] infer_stack: every uint8 / uint16 frame is contrast-enhanced on the device before its min / max
     # (utils/clahe.py: the library-exact CLAHE of the reference's ContrastEnhancement) and goes on as a uint16 frame
     apply_clahe = False
+    # [extension] cell_table: links between frames that share fewer pixels are dropped (inference/cells.py)
+    min_overlap = 1
 
     def __init__(self, img_id_list=None, inference_path=None, omero_username=None, omero_password=None, omero_host=None,
                  omero_port=None, group_id=None,
@@ -560,6 +562,19 @@ class InferWorker(QObject):
                     rois.append({'theZ': 0, 'theT': int(frame), 'theC': int(self.channel), 'fillColor': 0,
                                  'strokeColor': self.STROKE_COLOR, 'points': points_string(polygon)})
         return rois
+
+    def cell_table(self, results, img=None, channels=None):
+        """ [extension] The per-cell table of a segmented stack (inference/cells.py ``measure_cells``): ``results`` are the
+        masks of ``infer_stack``, ``img`` the [T, C, H, W] image (a strided view is read in place) whose ``channels``
+        (numbers of the source image, they name the columns) are measured.  Overlap linking: no motion model, no gap
+        closing. """
+        from .cells import measure_cells
+        df = measure_cells(results, img, link=True, min_overlap=self.min_overlap, device=self.device)
+        if img is not None and channels is not None:      # the view holds the chosen channels only: name them by source
+            names = {f'{k}_ch{i}': f'{k}_ch{int(c)}' for i, c in reversed(list(enumerate(channels)))
+                     for k in ('mean', 'std', 'min', 'max', 'sum', 'bg_mean')}
+            df = df.rename(columns=names)
+        return df
 
     def save_results(self, results_array, image_name, result_path=None, with_rois=False):
         """ ``<result_path>/<image stem>_channel<c>.tif`` (uint16 [T, H, W], the reference's local-save route) and, with
