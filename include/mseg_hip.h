@@ -616,6 +616,33 @@ int mseg_crops_overlay(const uint8_t* show, const uint8_t* outlines, uint8_t* rg
 int mseg_set_gather(const void* src, int src_dtype, long long n, long long HW, const int32_t* idx_dev, int N, void* dst,
                     int dst_mode, float lo, float hi, void* stream);
 
+/* ---- test-time augmentation for inference (csrc/tta.hip) — an extension, the reference has none ---------
+ * Transform codes are those of mseg_aug_flip, extended to rectangles; for a plane a of H x W:
+ *   0 a, 1 fliplr, 2 flipud, 3 rot90, 4 rot180, 5 rot270, 6 rot90(fliplr(a)) = a.T, 7 rot90(flipud(a))   (numpy's names)
+ * 3, 5, 6 and 7 transpose (their result is W x H); the inverse of 3 is 5 and of 5 is 3, every other code is its own.
+ * mseg_tta_expand: src [n][H0][W0] uint8 (MSEG_PIX_U8) / uint16 (MSEG_PIX_U16) with minmax [n][2] from mseg_frames_minmax,
+ *   or fp32 (MSEG_PIX_F32: already normalised, minmax ignored); codes: k <= 8 codes on the HOST, all transposing or all
+ *   not (MSEG_EINVAL otherwise, nothing is launched).  out fp32 [k][n][Hm + pad_top][Wm + pad_left], Hm x Wm = H0 x W0
+ *   or W0 x H0: member m of frame f is T_code[m](f), padded top / left with the value the host formula gives the pad
+ *   value `min` (-1) and normalised with the frame's own extrema — every value is the bits mseg_frames_normalize gives
+ *   for the transformed frame.  One launch whatever n and k; every element of out is written once.
+ * mseg_tta_merge: dst(f, ch, y, x) = (((p_0 + p_1) + p_2) + ... + p_{k-1}) * (1 / k), fp32 in descriptor order, p_m =
+ *   member m's prediction mapped back by the inverse of its code.  A descriptor's ptr is element (frame 0, channel 0,
+ *   row 0, pixel 0) of the member's un-padded prediction, in the member's own orientation (W x H for a transposing
+ *   code), and the strides are in elements; dst has its own four strides, so CHW planes and HWC-3 probabilities go
+ *   through the same kernel.  k in {1, 2, 4, 8} (the scale is exact), n <= 65535.  No atomics, no workspace; every source
+ *   element is read once, every destination element stored once.  Offsets are 64-bit.                                  */
+typedef struct MsegTtaMember {
+  const float* ptr;
+  int64_t frame_stride, chan_stride, row_stride, pix_stride;
+  int32_t code;
+  int32_t reserved;
+} MsegTtaMember;
+int mseg_tta_expand(const void* src, int dtype, int n, int H0, int W0, const uint32_t* minmax, const int32_t* codes, int k,
+                    int pad_top, int pad_left, float* out, void* stream);
+int mseg_tta_merge(const MsegTtaMember* members, int k, int n, int C, int H, int W, float* dst, long long dst_frame_stride,
+                   long long dst_chan_stride, long long dst_row_stride, long long dst_pix_stride, void* stream);
+
 /* ---- misc ---------------------------------------------------------------------------------------------------- */
 int mseg_version(void);
 const char* mseg_strerror(int code);

@@ -7,7 +7,8 @@ Same flags and output as the reference ``infer_script_local.py`` (:17-25, :164-1
 the GUI's Export button (inference/result_export.py) for the segmented channel of uint8 / uint16 stacks;
 ``--frame_batch N`` sends the frames of a stack through the network and the post-processing in groups of N;
 ``--clahe`` enhances every uint8 / uint16 frame first, like the reference's ``ContrastEnhancement(apply_clahe=True)``;
-``--cells`` adds ``mask_<stem>_channel<c>_cells.csv``, one row per cell and frame (inference/cells.py).
+``--cells`` adds ``mask_<stem>_channel<c>_cells.csv``, one row per cell and frame (inference/cells.py);
+``--tta K`` segments the average of the predictions of K flipped / rotated copies of every frame (inference/tta.py).
 """
 import argparse
 from pathlib import Path
@@ -85,6 +86,11 @@ def build_parser():
                              'the reference\'s ContrastEnhancement(apply_clahe=True), i.e. scikit-image\'s '
                              'equalize_adapthist(clip_limit=0.01), bit for bit; uint8 / uint16 images only, other stacks are '
                              'segmented without it')
+    parser.add_argument('--tta', default=1, type=int, choices=[1, 2, 4, 8],
+                        help='[extension] test-time augmentation: every frame is predicted under K flips / rotations '
+                             '(2: + left-right flip; 4: + up-down flip and 180 degrees; 8: all symmetries of the square), '
+                             'the predictions are mapped back and averaged, and the average is segmented.  K network '
+                             'forwards per frame; whole-frame inference only (not with --sliding_window).  1 = off')
     parser.add_argument('--rois', default=False, action='store_true',
                         help='[extension] also write <mask file stem>_rois.json: one polygon ROI per cell and frame, the '
                              'records the OMERO route of infer_script.py uploads (traced on the device)')
@@ -146,6 +152,9 @@ def main():
     worker.frame_batch = args.frame_batch
     worker.apply_clahe = args.clahe
     worker.min_overlap = args.min_overlap
+    worker.tta = args.tta
+    if args.tta > 1:
+        print(f'Test-time augmentation: {args.tta} network forwards per frame')
     worker.text_output.connect(print)
     torch.set_grad_enabled(False)
     print('--- Start inference ---')

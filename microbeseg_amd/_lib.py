@@ -68,6 +68,11 @@ class MsegRangerJob(C.Structure):
                 ("reserved", C.c_uint32)]
 
 
+class MsegTtaMember(C.Structure):
+    _fields_ = [("ptr", C.c_void_p), ("frame_stride", C.c_int64), ("chan_stride", C.c_int64), ("row_stride", C.c_int64),
+                ("pix_stride", C.c_int64), ("code", C.c_int32), ("reserved", C.c_int32)]
+
+
 _P = C.c_void_p
 _I = C.c_int
 _F = C.c_float
@@ -178,6 +183,9 @@ SIGNATURES = {
     "mseg_crop_census": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _SZ, _P]),
     "mseg_crops_overlay": (_I, [_P, _P, _P, _I, _I, _P]),
     "mseg_set_gather": (_I, [_P, _I, C.c_longlong, C.c_longlong, _P, _I, _P, _I, _F, _F, _P]),
+    "mseg_tta_expand": (_I, [_P, _I, _I, _I, _I, _P, C.POINTER(C.c_int32), _I, _I, _I, _P, _P]),
+    "mseg_tta_merge": (_I, [C.POINTER(MsegTtaMember), _I, _I, _I, _I, _I, _P, C.c_longlong, C.c_longlong, C.c_longlong,
+                            C.c_longlong, _P]),
     "mseg_version": (_I, []),
     "mseg_strerror": (C.c_char_p, [_I]),
     "mseg_last_hip_error": (_I, []),

@@ -93,6 +93,10 @@ class InferWorker(QObject):
     apply_clahe = False
     # [extension] cell_table: links between frames that share fewer pixels are dropped (inference/cells.py)
     min_overlap = 1
+    # [extension] test-time augmentation (inference/tta.py): 1 = off (no existing route changes), 2 / 4 / 8 =
+    # every frame is predicted under that many flips / rotations, the predictions are mapped back and averaged (fp32, in
+    # member order) and the average is segmented: K network forwards per frame.  Whole-frame inference only
+    tta = 1
 
     def __init__(self, img_id_list=None, inference_path=None, omero_username=None, omero_password=None, omero_host=None,
                  omero_port=None, group_id=None,
@@ -141,6 +145,8 @@ class InferWorker(QObject):
         :param pads: [rows padded at the top, columns padded at the left] (removed after the forward pass).
         :return: instance mask, np.uint16, shape of the un-padded frame.
         """
+        if self.tta != 1:               # the padding is the frame's own: every member is padded in its orientation
+            return self._infer_stack_tta(np.asarray(img)[None, pads[0]:, pads[1]:])[0]
         self.net.eval()
         # 2 * (f32(img) - min) / (max - min) - 1, same operation order and scalar types as infer.py:346-348
         img_batch = 2 * (img.astype(np.float32) - min_val) / (max_val - min_val) - 1
@@ -251,6 +257,162 @@ class InferWorker(QObject):
             out.append((i, m, pred))
             i += m
         return out, size
+
+    # -- [extension] test-time augmentation (inference/tta.py) ---------------------------------------------
+    def _tta_member_codes(self):
+        """member codes of ``self.tta``; raises before anything is launched if the route cannot take them"""
+        from . import tta as T
+        codes = T.member_codes(self.tta)
+        if len(codes) > 1 and self.sliding_window:
+            raise RuntimeError("test-time augmentation (tta > 1) needs whole-frame inference: tiled (sliding_window) "
+                               "TTA is not implemented")
+        if self.device.type != 'cuda':
+            raise RuntimeError("test-time augmentation runs on the GPU: there is no CPU path")
+        if self.model_settings is None or self.model_settings['label_type'] not in ('distance', 'boundary'):
+            raise RuntimeError("test-time augmentation needs a distance or boundary model")
+        return codes
+
+    def predict_merged(self, frames):
+        """[n, H, W] host array -> the merged prediction of the n frames on the device, without padding: distance models
+        (border, cell), each (n, H, W); boundary models the softmax probabilities (n, H, W, 3).  The n frames are ONE
+        group: per shape class their members go through the network member-major, in chunks of at most
+        ``tta.chunk_members(...)[0]``; a frame with a member that did not fit in memory gets zeros."""
+        return self._predict_merged(np.asarray(frames))[0]
+
+    def _predict_merged(self, frames, clahe=False):
+        """-> (merged prediction, [frame failed?])"""
+        from ..utils.utils import pad_amounts
+        from . import tta as T
+        codes = self._tta_member_codes()
+        if frames.ndim != 3 or frames.shape[0] == 0:
+            raise RuntimeError("predict_merged: a [n, H, W] array expected")
+        n, H, W = (int(v) for v in frames.shape)
+        boundary = self.model_settings['label_type'] == 'boundary'
+        lib = _lib.load()
+        self.net.eval()
+        with torch.cuda.device(self.device), torch.no_grad():
+            stream = torch.cuda.current_stream().cuda_stream
+            if frames.dtype in (np.uint8, np.uint16):
+                pad_amounts((H, W))                              # frames beyond 8192 raise here, like every whole-frame route
+                host = np.ascontiguousarray(frames)
+                raw = torch.from_numpy(host.view(np.int16) if host.dtype == np.uint16 else host).to(self.device)
+                if clahe:                                        # on the un-transformed frames; uint16 from here on
+                    from ..utils.clahe import clahe_device
+                    raw = clahe_device(raw)
+                minmax = torch.empty((n, 2), dtype=torch.int32, device=self.device)
+                _lib.check(lib.mseg_frames_minmax(raw.data_ptr(), engine.RawFrame.PIX[raw.dtype], n, H * W,
+                                                  minmax.data_ptr(), stream), "frames_minmax")
+            else:                                                # normalised un-padded on the host, as inference() does
+                xs = []
+                for frame in frames:
+                    fmin, fmax = np.min(frame), np.max(frame)
+                    xs.append((2 * (frame.astype(np.float32) - fmin) / (fmax - fmin) - 1).astype(np.float32))
+                raw, minmax = torch.from_numpy(np.ascontiguousarray(np.stack(xs))).to(self.device), None
+            failed = [False] * n
+            members, keep = {}, []
+            for cs, (hm, wm), pads in T.shape_classes(codes, H, W):
+                x = T.expand(raw, cs, pads, minmax)
+                hp, wp = int(x.shape[2]), int(x.shape[3])
+                x = x.view(len(cs) * n, 1, hp, wp)
+                m, _ = T.chunk_members(hp, wp, self.frame_batch, len(codes))
+                pieces = []
+                for c0 in range(0, x.shape[0], m):
+                    chunks, _ = self._forward_group(x[c0:c0 + m])
+                    pieces += [(c0 + i, cnt, pred) for i, cnt, pred in chunks]
+                pred = self._tta_join(pieces, n, failed, 3 if boundary else 1, hp, wp)
+                if boundary:
+                    logits = pred.contiguous()
+                    probs = torch.empty((len(cs) * n, hm, wm, 3), dtype=torch.float32, device=self.device)
+                    for j in range(len(cs) * n):
+                        _lib.check(lib.mseg_softmax3_hwc(logits[j].data_ptr(), hp, wp, pads[0], pads[1],
+                                                         probs[j].data_ptr(), stream), "softmax3_hwc")
+                    keep += [logits, probs]
+                    for ci, code in enumerate(cs):
+                        members[code] = T.member(probs.permute(0, 3, 1, 2), code, first=ci * n)
+                else:
+                    keep += list(pred)
+                    for ci, code in enumerate(cs):
+                        members[code] = tuple(T.member(t, code, first=ci * n, pads=pads) for t in pred)
+            order = sorted(members)
+            if boundary:
+                merged = T.merge([members[c] for c in order], n, 3, H, W, hwc=True)
+            else:
+                merged = tuple(T.merge([members[c][h] for c in order], n, 1, H, W)[:, 0] for h in (0, 1))
+            del keep                                             # (alive until the merges were enqueued on this stream)
+            if any(failed):
+                bad = torch.tensor(failed, device=self.device)
+                for t in (merged if isinstance(merged, tuple) else (merged,)):
+                    t[bad] = 0
+        return merged, failed
+
+    def _tta_join(self, pieces, n, failed, ch, hp, wp):
+        """the predictions of a class's members from the pieces its forwards came in; a piece that did not fit in memory
+        becomes zeros and marks its frames (member j belongs to frame j % n)"""
+        if len(pieces) == 1 and pieces[0][2] is not None:
+            return pieces[0][2]
+        heads = 1 if ch == 3 else 2
+        parts = [[] for _ in range(heads)]
+        for j0, cnt, pred in pieces:
+            if pred is None:
+                for j in range(j0, j0 + cnt):
+                    failed[j % n] = True
+                pred = tuple(torch.zeros((cnt, ch, hp, wp), dtype=torch.float32, device=self.device) for _ in range(heads))
+            elif heads == 1:
+                pred = (pred,)
+            for h in range(heads):
+                parts[h].append(pred[h])
+        joined = tuple(torch.cat(p, dim=0) for p in parts)
+        return joined[0] if heads == 1 else joined
+
+    def _infer_stack_tta(self, img):
+        """infer_stack with ``tta > 1``: group after group on the main stream — upload, expand, one forward per shape
+        class (and chunk), merge, hook, the batched post-processing, masks back through one pinned buffer.  No side
+        streams: nothing of a group overlaps the next one."""
+        from ..utils.utils import pad_amounts
+        from . import tta as T
+        codes = self._tta_member_codes()
+        T_, H, W = (int(v) for v in img.shape)
+        results = np.zeros(shape=(T_, H, W), dtype=np.uint16)
+        if T_ == 0:
+            return results
+        boundary = self.model_settings['label_type'] == 'boundary'
+        clahe = self._clahe_enabled(img)
+        pads = pad_amounts((H, W))
+        _, group = T.chunk_members(H + pads[0], W + pads[1], self.frame_batch, len(codes))
+        group = min(group, T_)
+        with torch.cuda.device(self.device), torch.no_grad():
+            host = torch.empty((group, H, W), dtype=torch.int16, pin_memory=True)
+            for f0 in range(0, T_, group):
+                if self.stop_inference:
+                    break
+                n = min(group, T_ - f0)
+                pred, failed = self._predict_merged(img[f0:f0 + n], clahe)
+                if self.prediction_hook is not None:      # once per frame, in frame order, on the merged prediction
+                    def hook(p, i):                       # (a frame that did not fit has no prediction: zero mask, no call)
+                        return p if failed[i] else self.prediction_hook(p)
+                    if boundary:
+                        pred = torch.cat([hook(pred[i:i + 1].permute(0, 3, 1, 2), i).permute(0, 2, 3, 1)
+                                          for i in range(n)], dim=0).contiguous()
+                    else:
+                        hooked = [hook((pred[0][i:i + 1, None], pred[1][i:i + 1, None]), i) for i in range(n)]
+                        pred = (torch.cat([h[0] for h in hooked], dim=0)[:, 0], torch.cat([h[1] for h in hooked], dim=0)[:, 0])
+                if boundary:
+                    for c0 in range(0, n, 8):
+                        outs = pp.boundary_postprocessing_batch_device([pred[i] for i in range(c0, min(c0 + 8, n))])
+                        for i, (labels, _, _) in enumerate(outs):
+                            host[c0 + i].copy_(labels, non_blocking=True)
+                else:
+                    labels, _, _ = pp.distance_postprocessing_batch_device(pred[0], pred[1], th_seed=self.ths[1],
+                                                                           th_cell=self.ths[0], pads=(0, 0),
+                                                                           col_major_ids=True)
+                    host[:n].copy_(labels, non_blocking=True)
+                torch.cuda.current_stream().synchronize()
+                results[f0:f0 + n] = host[:n].numpy().view(np.uint16)
+                for i in range(n):
+                    if failed[i]:
+                        results[f0 + i] = 0
+                    self.progress.emit(int(100 * (f0 + i + 1) / T_))
+        return results
 
     def _clahe_enabled(self, img):
         """apply_clahe for this stack?  Float stacks are segmented without it (no fixed grey-level range), with a message"""
@@ -387,6 +549,8 @@ class InferWorker(QObject):
         (a few long-running, latency-bound lanes) runs on the side stream, the matrix kernels of frame i+1 run on the
         main stream, and the uint16 mask travels back through a pinned buffer.  Results are identical to calling
         ``inference`` frame by frame."""
+        if self.tta != 1:
+            return self._infer_stack_tta(img)
         results = np.zeros(shape=(img.shape[0], img.shape[1], img.shape[2]), dtype=np.uint16)
         pipelined = (self.model_settings is not None and self.model_settings['label_type'] in ('distance', 'boundary')
                      and self.device.type == 'cuda')
