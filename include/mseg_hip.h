@@ -643,6 +643,39 @@ int mseg_tta_expand(const void* src, int dtype, int n, int H0, int W0, const uin
 int mseg_tta_merge(const MsegTtaMember* members, int k, int n, int C, int H, int W, float* dst, long long dst_frame_stride,
                    long long dst_chan_stride, long long dst_row_stride, long long dst_pix_stride, void* stream);
 
+/* ---- inference at a chosen resolution (csrc/resample.hip) — an extension ---------------------------------
+ * Separable, anti-aliased linear resampling with pixel-centre alignment.  The rule is a table per axis, made on the HOST
+ * (inference/resample.py axis_table): output index i takes count[i] <= taps source elements from first[i] on, with the
+ * fp32 weights weight[i][0 .. taps) (zero beyond count[i]).  MsegResampleAxis carries the table on the device (first,
+ * count, weight) and the same first / count on the host: the call validates the host copy (1 <= taps <= 12, n_out > 0,
+ * 1 <= count <= taps, every window inside [0, n_in), first and first + count not decreasing) and sizes its tiles from it;
+ * anything else is MSEG_EINVAL and nothing is launched.  The kernels compute no weights.  A value is
+ * sum_y w_y (sum_x w_x v): fp32 fmaf from 0 in ascending tap order, x before y; it does not depend on the tile, the launch
+ * or the other frames of the launch.  One launch whatever n; every destination element is stored once; no atomics, no
+ * workspace; offsets are 64-bit; n <= 65535.
+ * mseg_resample_frames: src [n][yaxis.n_in][xaxis.n_in] uint8 (MSEG_PIX_U8) / uint16 (MSEG_PIX_U16) with minmax [n][2] from
+ *   mseg_frames_minmax, or fp32 (MSEG_PIX_F32: already normalised, minmax ignored).  A raw pixel enters the filter as the
+ *   value mseg_frames_normalize gives it.  out fp32 [n][yaxis.n_out + pad_top][xaxis.n_out + pad_left]; the top / left
+ *   padding is -1, the normalised frame minimum.
+ * mseg_resample_planes: src is element (frame 0, channel 0, row 0, pixel 0) of the un-padded source, yaxis.n_in x xaxis.n_in
+ *   per frame and channel, with four strides in elements; dst is yaxis.n_out x xaxis.n_out with its own four strides, so
+ *   CHW planes and HWC-3 probabilities go through the same kernel.                                                        */
+typedef struct MsegResampleAxis {
+  const int32_t* first;        /* device [n_out] */
+  const int32_t* count;        /* device [n_out] */
+  const float* weight;         /* device [n_out][taps] */
+  const int32_t* host_first;   /* host copy of first */
+  const int32_t* host_count;   /* host copy of count */
+  int32_t n_in, n_out, taps;
+  int32_t reserved;
+} MsegResampleAxis;
+int mseg_resample_frames(const void* src, int dtype, int n, const uint32_t* minmax, const MsegResampleAxis* yaxis,
+                         const MsegResampleAxis* xaxis, int pad_top, int pad_left, float* out, void* stream);
+int mseg_resample_planes(const float* src, long long src_frame_stride, long long src_chan_stride, long long src_row_stride,
+                         long long src_pix_stride, int n, int C, const MsegResampleAxis* yaxis,
+                         const MsegResampleAxis* xaxis, float* dst, long long dst_frame_stride, long long dst_chan_stride,
+                         long long dst_row_stride, long long dst_pix_stride, void* stream);
+
 /* ---- misc ---------------------------------------------------------------------------------------------------- */
 int mseg_version(void);
 const char* mseg_strerror(int code);

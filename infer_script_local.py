@@ -8,7 +8,8 @@ the GUI's Export button (inference/result_export.py) for the segmented channel o
 ``--frame_batch N`` sends the frames of a stack through the network and the post-processing in groups of N;
 ``--clahe`` enhances every uint8 / uint16 frame first, like the reference's ``ContrastEnhancement(apply_clahe=True)``;
 ``--cells`` adds ``mask_<stem>_channel<c>_cells.csv``, one row per cell and frame (inference/cells.py);
-``--tta K`` segments the average of the predictions of K flipped / rotated copies of every frame (inference/tta.py).
+``--tta K`` segments the average of the predictions of K flipped / rotated copies of every frame (inference/tta.py);
+``--scale S`` predicts every frame at S times its resolution and segments at its own (inference/resample.py).
 """
 import argparse
 from pathlib import Path
@@ -61,8 +62,30 @@ def select_channels(img, channels, name):
     return view[:, list(channels)]
 
 
+def scale_argument(text):
+    """--scale: a real number in [0.25, 4] (the rule of InferWorker.scale)"""
+    from microbeseg_amd.inference.resample import check_scale
+    try:
+        return check_scale(float(text))
+    except ValueError as err:
+        raise argparse.ArgumentTypeError(str(err))
+
+
+class Parser(argparse.ArgumentParser):
+    """reports the combinations the worker would refuse as command-line errors, before a model is loaded"""
+
+    def parse_args(self, args=None, namespace=None):
+        ns = super().parse_args(args, namespace)
+        if ns.scale != 1:
+            if ns.tta > 1:
+                self.error('--scale and --tta > 1 cannot be combined')
+            if ns.sliding_window:
+                self.error('--scale and --sliding_window cannot be combined')
+        return ns
+
+
 def build_parser():
-    parser = argparse.ArgumentParser(description='microbeSEG inference on local files (MI355X-native hot path)')
+    parser = Parser(description='microbeSEG inference on local files (MI355X-native hot path)')
     parser.add_argument('--img_dir', '-i', required=True, type=str, help='Directory with .tif images / stacks')
     parser.add_argument('--model', '-m', required=True, type=str, help='Model to use (path without suffix)')
     parser.add_argument('--thresholds', '-t', default=[0.10, 0.45], nargs='+', type=float,
@@ -91,6 +114,13 @@ def build_parser():
                              '(2: + left-right flip; 4: + up-down flip and 180 degrees; 8: all symmetries of the square), '
                              'the predictions are mapped back and averaged, and the average is segmented.  K network '
                              'forwards per frame; whole-frame inference only (not with --sliding_window).  1 = off')
+    parser.add_argument('--scale', default=1.0, type=scale_argument,
+                        help='[extension] predict at another resolution: every frame is resampled to S times its size on '
+                             'the device (anti-aliased linear), predicted there, and the prediction is resampled back and '
+                             'segmented at the frame\'s own resolution, so the mask has the frame\'s size and the '
+                             'thresholds keep their meaning.  For images of another magnification than the training data; '
+                             'S < 1 is also faster.  0.25 <= S <= 4; whole-frame inference only (not with --sliding_window '
+                             'or --tta > 1).  1 = off')
     parser.add_argument('--rois', default=False, action='store_true',
                         help='[extension] also write <mask file stem>_rois.json: one polygon ROI per cell and frame, the '
                              'records the OMERO route of infer_script.py uploads (traced on the device)')
@@ -153,6 +183,9 @@ def main():
     worker.apply_clahe = args.clahe
     worker.min_overlap = args.min_overlap
     worker.tta = args.tta
+    worker.scale = args.scale
+    if args.scale != 1:
+        print(f'Inference at {args.scale} x the resolution of the frames')
     if args.tta > 1:
         print(f'Test-time augmentation: {args.tta} network forwards per frame')
     worker.text_output.connect(print)

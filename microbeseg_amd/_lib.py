@@ -73,6 +73,12 @@ class MsegTtaMember(C.Structure):
                 ("pix_stride", C.c_int64), ("code", C.c_int32), ("reserved", C.c_int32)]
 
 
+class MsegResampleAxis(C.Structure):
+    _fields_ = [("first", C.c_void_p), ("count", C.c_void_p), ("weight", C.c_void_p), ("host_first", C.c_void_p),
+                ("host_count", C.c_void_p), ("n_in", C.c_int32), ("n_out", C.c_int32), ("taps", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 _P = C.c_void_p
 _I = C.c_int
 _F = C.c_float
@@ -186,6 +192,10 @@ SIGNATURES = {
     "mseg_tta_expand": (_I, [_P, _I, _I, _I, _I, _P, C.POINTER(C.c_int32), _I, _I, _I, _P, _P]),
     "mseg_tta_merge": (_I, [C.POINTER(MsegTtaMember), _I, _I, _I, _I, _I, _P, C.c_longlong, C.c_longlong, C.c_longlong,
                             C.c_longlong, _P]),
+    "mseg_resample_frames": (_I, [_P, _I, _I, _P, C.POINTER(MsegResampleAxis), C.POINTER(MsegResampleAxis), _I, _I, _P, _P]),
+    "mseg_resample_planes": (_I, [_P, C.c_longlong, C.c_longlong, C.c_longlong, C.c_longlong, _I, _I,
+                                  C.POINTER(MsegResampleAxis), C.POINTER(MsegResampleAxis), _P, C.c_longlong, C.c_longlong,
+                                  C.c_longlong, C.c_longlong, _P]),
     "mseg_version": (_I, []),
     "mseg_strerror": (C.c_char_p, [_I]),
     "mseg_last_hip_error": (_I, []),

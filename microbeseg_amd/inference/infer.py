@@ -97,6 +97,12 @@ class InferWorker(QObject):
     # every frame is predicted under that many flips / rotations, the predictions are mapped back and averaged (fp32, in
     # member order) and the average is segmented: K network forwards per frame.  Whole-frame inference only
     tta = 1
+    # [extension] inference at a chosen resolution (inference/resample.py): 1.0 = off (no existing route
+    # changes), a real number in [0.25, 4] otherwise: every frame is resampled to out_size(H, scale) x out_size(W, scale) on
+    # the device (anti-aliased linear), predicted there, the prediction is resampled back to H x W and segmented at the
+    # frame's own resolution, so thresholds and seed sizes keep their meaning in original pixels.  Whole-frame inference
+    # only, not together with tta
+    scale = 1.0
 
     def __init__(self, img_id_list=None, inference_path=None, omero_username=None, omero_password=None, omero_host=None,
                  omero_port=None, group_id=None,
@@ -145,6 +151,8 @@ class InferWorker(QObject):
         :param pads: [rows padded at the top, columns padded at the left] (removed after the forward pass).
         :return: instance mask, np.uint16, shape of the un-padded frame.
         """
+        if self.scale != 1 or isinstance(self.scale, bool):     # the padding is the frame's own: the scaled frame gets its own
+            return self._infer_stack_scaled(np.asarray(img)[None, pads[0]:, pads[1]:])[0]
         if self.tta != 1:               # the padding is the frame's own: every member is padded in its orientation
             return self._infer_stack_tta(np.asarray(img)[None, pads[0]:, pads[1]:])[0]
         self.net.eval()
@@ -414,6 +422,135 @@ class InferWorker(QObject):
                     self.progress.emit(int(100 * (f0 + i + 1) / T_))
         return results
 
+    # -- [extension] inference at a chosen resolution (inference/resample.py) ------------------------------
+    def _scale_checked(self):
+        """``self.scale`` as a float; raises before anything is launched if the value or the route cannot be taken"""
+        from . import resample as R
+        s = R.check_scale(self.scale)
+        if s != 1.0:
+            if self.sliding_window:
+                raise RuntimeError("inference at a chosen resolution (scale != 1) needs whole-frame inference: tiled "
+                                   "(sliding_window) scaled inference is not implemented")
+            if self.tta != 1:
+                raise RuntimeError("inference at a chosen resolution (scale != 1) and test-time augmentation (tta > 1) "
+                                   "are not implemented together")
+        if self.device.type != 'cuda':
+            raise RuntimeError("inference at a chosen resolution runs on the GPU: there is no CPU path")
+        if self.model_settings is None or self.model_settings['label_type'] not in ('distance', 'boundary'):
+            raise RuntimeError("inference at a chosen resolution needs a distance or boundary model")
+        return s
+
+    def _scaled_geometry(self, H, W, s):
+        """-> ((Hs, Ws), pads of the scaled frame, y table, x table forwards, y table, x table back)"""
+        from ..utils.utils import pad_amounts
+        from . import resample as R
+        hs, ws = R.out_size(H, s), R.out_size(W, s)
+        pads = [int(p) for p in pad_amounts((hs, ws))]           # a scaled frame beyond 8192 raises here
+        dev = self.device
+        return (hs, ws), pads, R.axis(H, hs, dev), R.axis(W, ws, dev), R.axis(hs, H, dev), R.axis(ws, W, dev)
+
+    def predict_scaled(self, frames):
+        """[n, H, W] host array -> the prediction of the n frames on THEIR grid, without padding, on the device: distance
+        models (border, cell), each (n, H, W); boundary models the softmax probabilities (n, H, W, 3).  The frames are
+        resampled to ``scale`` on the device, go through the network as ONE group (halved if memory runs out) and the
+        prediction is resampled back; a frame that did not fit in memory gets zeros."""
+        return self._predict_scaled(np.asarray(frames))[0]
+
+    def _predict_scaled(self, frames, clahe=False):
+        """-> (prediction at the frames' resolution, [frame failed?])"""
+        from . import resample as R
+        s = self._scale_checked()
+        if frames.ndim != 3 or frames.shape[0] == 0:
+            raise RuntimeError("predict_scaled: a [n, H, W] array expected")
+        n, H, W = (int(v) for v in frames.shape)
+        boundary = self.model_settings['label_type'] == 'boundary'
+        lib = _lib.load()
+        self.net.eval()
+        with torch.cuda.device(self.device), torch.no_grad():
+            (hs, ws), pads, ydown, xdown, yup, xup = self._scaled_geometry(H, W, s)
+            stream = torch.cuda.current_stream().cuda_stream
+            if frames.dtype in (np.uint8, np.uint16):
+                host = np.ascontiguousarray(frames)
+                raw = torch.from_numpy(host.view(np.int16) if host.dtype == np.uint16 else host).to(self.device)
+                if clahe:                                        # on the frames as recorded; uint16 from here on
+                    from ..utils.clahe import clahe_device
+                    raw = clahe_device(raw)
+                minmax = torch.empty((n, 2), dtype=torch.int32, device=self.device)
+                _lib.check(lib.mseg_frames_minmax(raw.data_ptr(), engine.RawFrame.PIX[raw.dtype], n, H * W,
+                                                  minmax.data_ptr(), stream), "frames_minmax")
+            else:                                                # normalised un-padded on the host, as inference() does
+                xs = []
+                for frame in frames:
+                    fmin, fmax = np.min(frame), np.max(frame)
+                    xs.append((2 * (frame.astype(np.float32) - fmin) / (fmax - fmin) - 1).astype(np.float32))
+                raw, minmax = torch.from_numpy(np.ascontiguousarray(np.stack(xs))).to(self.device), None
+            x = R.frames(raw, ydown, xdown, pads, minmax)
+            hp, wp = int(x.shape[1]), int(x.shape[2])
+            chunks, _ = self._forward_group(x.view(n, 1, hp, wp))
+            failed = [False] * n
+            pred = self._tta_join(chunks, n, failed, 3 if boundary else 1, hp, wp)
+            if boundary:
+                logits = pred.contiguous()
+                probs = torch.empty((n, hs, ws, 3), dtype=torch.float32, device=self.device)
+                for j in range(n):
+                    _lib.check(lib.mseg_softmax3_hwc(logits[j].data_ptr(), hp, wp, pads[0], pads[1], probs[j].data_ptr(),
+                                                     stream), "softmax3_hwc")
+                out = R.planes(probs.permute(0, 3, 1, 2), yup, xup, hwc=True)
+            else:
+                out = tuple(R.planes(t, yup, xup, pads=pads)[:, 0] for t in pred)
+            if any(failed):
+                bad = torch.tensor(failed, device=self.device)
+                for t in (out if isinstance(out, tuple) else (out,)):
+                    t[bad] = 0
+        return out, failed
+
+    def _infer_stack_scaled(self, img):
+        """infer_stack with ``scale != 1``: group after group on the main stream — upload, resample, one forward, resample
+        back, hook, the batched post-processing at the frame's resolution, masks back through one pinned buffer.  No side
+        streams: nothing of a group overlaps the next one."""
+        s = self._scale_checked()
+        T_, H, W = (int(v) for v in img.shape)
+        results = np.zeros(shape=(T_, H, W), dtype=np.uint16)
+        if T_ == 0:
+            return results
+        boundary = self.model_settings['label_type'] == 'boundary'
+        clahe = self._clahe_enabled(img)
+        (hs, ws), pads = self._scaled_geometry(H, W, s)[:2]
+        group = min(frame_batch_for(hs + pads[0], ws + pads[1], self.frame_batch), T_)
+        with torch.cuda.device(self.device), torch.no_grad():
+            host = torch.empty((group, H, W), dtype=torch.int16, pin_memory=True)
+            for f0 in range(0, T_, group):
+                if self.stop_inference:
+                    break
+                n = min(group, T_ - f0)
+                pred, failed = self._predict_scaled(img[f0:f0 + n], clahe)
+                if self.prediction_hook is not None:      # once per frame, in frame order, on the full-resolution prediction
+                    def hook(p, i):                       # (a frame that did not fit has no prediction: zero mask, no call)
+                        return p if failed[i] else self.prediction_hook(p)
+                    if boundary:
+                        pred = torch.cat([hook(pred[i:i + 1].permute(0, 3, 1, 2), i).permute(0, 2, 3, 1)
+                                          for i in range(n)], dim=0).contiguous()
+                    else:
+                        hooked = [hook((pred[0][i:i + 1, None], pred[1][i:i + 1, None]), i) for i in range(n)]
+                        pred = (torch.cat([h[0] for h in hooked], dim=0)[:, 0], torch.cat([h[1] for h in hooked], dim=0)[:, 0])
+                if boundary:
+                    for c0 in range(0, n, 8):
+                        outs = pp.boundary_postprocessing_batch_device([pred[i] for i in range(c0, min(c0 + 8, n))])
+                        for i, (labels, _, _) in enumerate(outs):
+                            host[c0 + i].copy_(labels, non_blocking=True)
+                else:
+                    labels, _, _ = pp.distance_postprocessing_batch_device(pred[0], pred[1], th_seed=self.ths[1],
+                                                                           th_cell=self.ths[0], pads=(0, 0),
+                                                                           col_major_ids=True)
+                    host[:n].copy_(labels, non_blocking=True)
+                torch.cuda.current_stream().synchronize()
+                results[f0:f0 + n] = host[:n].numpy().view(np.uint16)
+                for i in range(n):
+                    if failed[i]:
+                        results[f0 + i] = 0
+                    self.progress.emit(int(100 * (f0 + i + 1) / T_))
+        return results
+
     def _clahe_enabled(self, img):
         """apply_clahe for this stack?  Float stacks are segmented without it (no fixed grey-level range), with a message"""
         if not self.apply_clahe:
@@ -549,6 +686,8 @@ class InferWorker(QObject):
         (a few long-running, latency-bound lanes) runs on the side stream, the matrix kernels of frame i+1 run on the
         main stream, and the uint16 mask travels back through a pinned buffer.  Results are identical to calling
         ``inference`` frame by frame."""
+        if self.scale != 1 or isinstance(self.scale, bool):
+            return self._infer_stack_scaled(img)
         if self.tta != 1:
             return self._infer_stack_tta(img)
         results = np.zeros(shape=(img.shape[0], img.shape[1], img.shape[2]), dtype=np.uint16)
