@@ -182,7 +182,7 @@ int mseg_first_conv_fwd(const float* x4, const float* w, const float* bias, int 
  *                            first layer does not take the kernel above                                                   */
 #define MSEG_PIX_U8 0
 #define MSEG_PIX_U16 1
-#define MSEG_PIX_I32 2 /* label stacks: mseg_stack_relabel, mseg_cell_measure, mseg_cell_links */
+#define MSEG_PIX_I32 2 /* label stacks: mseg_stack_relabel, mseg_cell_measure, mseg_cell_links, mseg_stack_drift */
 #define MSEG_PIX_F32 3 /* mseg_clahe_u16 only: fp32 holding the integers 0..65535 */
 int mseg_frame_minmax(const void* raw, int dtype, size_t npix, uint32_t* minmax, void* stream);
 int mseg_first_conv_fwd_raw(const void* raw, int dtype, int H0, int W0, int pad_top, int pad_left, const uint32_t* minmax,
@@ -567,6 +567,28 @@ size_t mseg_cell_links_workspace_bytes(int T, int64_t n_labels, int64_t table_ca
 int mseg_cell_links(const void* labels, int dtype, int T, int H, int W, const int64_t* label_off, int64_t n_labels,
                     int64_t table_cap, int32_t* pred, int32_t* overlap, int32_t* status, void* ws, size_t ws_bytes,
                     void* stream);
+
+/* ---- drift-compensated linking (csrc/drift.hip, csrc/cells.hip) — an extension ---------------------------
+ * labels, dtype and label_off as for mseg_cell_links.  A pixel is foreground, F_t(y, x), when its id is in 1 .. K_t (ids
+ * beyond the frame's table and negative ids are background).
+ * mseg_stack_drift: R = max_drift, 0 <= R <= 128; scores: uint32 [T - 1][2R + 1][2R + 1] on the device, written whole by
+ *   the call; for the pair (t - 1, t), t >= 1:
+ *     scores[t - 1][dy + R][dx + R] = #{(y, x): 0 <= y < H, 0 <= x < W, 0 <= y - dy < H, 0 <= x - dx < W,
+ *                                              F_t(y, x) and F_{t-1}(y - dy, x - dx)}
+ *   = the foreground of frame t - 1 moved by (dy, dx) and laid over the foreground of frame t; pixels moved out of the
+ *   frame count nothing.  T == 1 writes nothing.  Integers only, independent of the order of arrival.  H * W < 2^31 - 512.
+ *   ws >= mseg_stack_drift_workspace_bytes (one bit per pixel, rows padded to 64-bit words + 5 words; 0 = bad arguments);
+ *   MSEG_EINVAL: bad arguments, R outside 0 .. 128, a dtype not listed; MSEG_EWORKSPACE: ws_bytes too small.
+ * mseg_cell_links_shifted: mseg_cell_links (same outputs, workspace, status word and tie rule) with another pairing: pixel
+ *   (y, x) of frame t pairs with (y - dy_t, x - dx_t) of frame t - 1, or with nothing where that lies outside the frame.
+ *   shift: int32 [T][2] = (dy_t, dx_t) on the device, entry 0 unused; any int32 is legal (|dy| >= H or |dx| >= W: no
+ *   pairs).  All shifts zero: the outputs of mseg_cell_links, byte for byte.                                             */
+size_t mseg_stack_drift_workspace_bytes(int T, int H, int W);
+int mseg_stack_drift(const void* labels, int dtype, int T, int H, int W, const int64_t* label_off, int max_drift,
+                     uint32_t* scores, void* ws, size_t ws_bytes, void* stream);
+int mseg_cell_links_shifted(const void* labels, int dtype, int T, int H, int W, const int64_t* label_off, int64_t n_labels,
+                            int64_t table_cap, const int32_t* shift, int32_t* pred, int32_t* overlap, int32_t* status,
+                            void* ws, size_t ws_bytes, void* stream);
 
 /* ---- training-set preparation (DataCropWorker src/utils/data_cropping.py:157-264,286,
  * DataImportWorker src/utils/data_import.py:125-194, DataExportWorker src/utils/data_export.py:100-101) -----------------

@@ -9,7 +9,8 @@ the GUI's Export button (inference/result_export.py) for the segmented channel o
 ``--clahe`` enhances every uint8 / uint16 frame first, like the reference's ``ContrastEnhancement(apply_clahe=True)``;
 ``--cells`` adds ``mask_<stem>_channel<c>_cells.csv``, one row per cell and frame (inference/cells.py);
 ``--tta K`` segments the average of the predictions of K flipped / rotated copies of every frame (inference/tta.py);
-``--scale S`` predicts every frame at S times its resolution and segments at its own (inference/resample.py).
+``--scale S`` predicts every frame at S times its resolution and segments at its own (inference/resample.py);
+``--drift [R]`` with ``--cells``: cells are linked under the stage drift found within +-R pixels (inference/cells.py).
 """
 import argparse
 from pathlib import Path
@@ -76,6 +77,11 @@ class Parser(argparse.ArgumentParser):
 
     def parse_args(self, args=None, namespace=None):
         ns = super().parse_args(args, namespace)
+        if ns.drift is not None:
+            if not ns.cells:
+                self.error('--drift needs --cells (it changes how the cell table links frames)')
+            if not 0 <= ns.drift <= 128:
+                self.error(f'--drift: a search radius of 0 .. 128 pixels expected, got {ns.drift}')
         if ns.scale != 1:
             if ns.tta > 1:
                 self.error('--scale and --tta > 1 cannot be combined')
@@ -142,6 +148,12 @@ def build_parser():
                              'images get the shape and link columns.  A channel an image does not have is an error')
     parser.add_argument('--min_overlap', default=1, type=int,
                         help='[extension] with --cells: links that share fewer pixels are dropped before tracks are built')
+    parser.add_argument('--drift', nargs='?', const=32, default=None, type=int,
+                        help='[extension] with --cells: take the stage drift out before linking.  For every frame pair the '
+                             'whole-pixel shift within +-R pixels (default R = 32, 0 <= R <= 128) under which the two '
+                             'masks overlap most is found on the device, cells are linked under it, and the table gains '
+                             'drift_y / drift_x (the shift against frame 0) and centroid_y_reg / centroid_x_reg.  '
+                             'Translation in whole pixels only: no rotation, no scaling, no registered image stack')
     return parser
 
 
@@ -182,8 +194,11 @@ def main():
     worker.frame_batch = args.frame_batch
     worker.apply_clahe = args.clahe
     worker.min_overlap = args.min_overlap
+    worker.drift = args.drift
     worker.tta = args.tta
     worker.scale = args.scale
+    if args.drift is not None:
+        print(f'Cell table: linking under the stage drift found within +-{args.drift} px per frame pair')
     if args.scale != 1:
         print(f'Inference at {args.scale} x the resolution of the frames')
     if args.tta > 1:

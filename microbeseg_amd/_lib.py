@@ -183,6 +183,9 @@ SIGNATURES = {
                                _P, _P, _P, _P, _P, _P, _P]),
     "mseg_cell_links_workspace_bytes": (_SZ, [_I, C.c_int64, C.c_int64]),
     "mseg_cell_links": (_I, [_P, _I, _I, _I, _I, _P, C.c_int64, C.c_int64, _P, _P, _P, _P, _SZ, _P]),
+    "mseg_cell_links_shifted": (_I, [_P, _I, _I, _I, _I, _P, C.c_int64, C.c_int64, _P, _P, _P, _P, _P, _SZ, _P]),
+    "mseg_stack_drift_workspace_bytes": (_SZ, [_I, _I, _I]),
+    "mseg_stack_drift": (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _P, _SZ, _P]),
     "mseg_frame_stats": (_I, [_P, _I, _SZ, _P, _P]),
     "mseg_crops_extract": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "mseg_crop_census_workspace_bytes": (_SZ, []),

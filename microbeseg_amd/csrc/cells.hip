@@ -5,6 +5,7 @@
 //                      integer sums of a regionprops row (area, first / second coordinate moments, bounding box) and per
 //                      cell and channel sum / sum of squares / min / max; the same per frame over the background
 //   mseg_cell_links    per cell of frame t the label of frame t - 1 that shares the most pixels with it
+//   mseg_cell_links_shifted  the same with frame t - 1 moved by a per-pair integer shift (drift compensation, §6o)
 // Everything is integer arithmetic with order-free 64-bit atomics: bit-identical from run to run.
 #include "common.h"
 
@@ -351,6 +352,48 @@ __global__ void __launch_bounds__(CM_BLOCK) cl_pairs_kernel(const L* __restrict_
   if (len) cl_insert(kt, ct, cap - 1, cl, cm, len, status + t);
 }
 
+// The pairs under a per-pair shift: pixel (y, x) of frame t pairs with (y - dy_t, x - dx_t) of frame t - 1.  A lane folds 8
+// consecutive pixels of ONE row of frame t (the shifted source is contiguous within a row only, so a run never crosses a
+// row end); the frame t - 1 pixels are in general unaligned and partly outside the frame: scalar loads under a bounds test.
+template <typename L>
+__global__ void __launch_bounds__(CM_BLOCK) cl_pairs_shifted_kernel(const L* __restrict__ lab, int T, int H, int W,
+                                                                    const int64_t* __restrict__ loff,
+                                                                    const int32_t* __restrict__ shift,
+                                                                    u64* __restrict__ keys, uint32_t* __restrict__ cnt,
+                                                                    uint32_t cap, int32_t* __restrict__ status) {
+  const int64_t per_row = ((int64_t)W + CM_PPL - 1) / CM_PPL, groups = (int64_t)H * per_row;
+  const int64_t g = (int64_t)blockIdx.x * CM_BLOCK + threadIdx.x;
+  if (g >= (int64_t)(T - 1) * groups) return;
+  const int t = (int)(g / groups) + 1;
+  const int64_t in_frame = g - (int64_t)(t - 1) * groups;
+  const int y = (int)(in_frame / per_row);
+  const int x0 = (int)(in_frame - (int64_t)y * per_row) * CM_PPL;
+  const int64_t ys = (int64_t)y - shift[2 * t], xs0 = (int64_t)x0 - shift[2 * t + 1];
+  if (ys < 0 || ys >= H || xs0 + CM_PPL <= 0 || xs0 >= W) return;      // no pixel of this lane has a source
+  const int nvalid = min(CM_PPL, W - x0);
+  const int64_t Kl = loff[t + 1] - loff[t], Km = loff[t] - loff[t - 1];
+  const L* pl = lab + ((int64_t)t * H + y) * W + x0;
+  const L* pm = lab + ((int64_t)(t - 1) * H + ys) * W;                  // the source row
+  int l[CM_PPL], m[CM_PPL];
+  cm_load8<L>(pl, nvalid, 1, nvalid == CM_PPL && ((uintptr_t)pl & 15) == 0, l);
+#pragma unroll
+  for (int k = 0; k < CM_PPL; ++k) {
+    const int64_t xs = xs0 + k;
+    m[k] = (k < nvalid && xs >= 0 && xs < W) ? (int)pm[xs] : 0;
+  }
+  u64* kt = keys + (size_t)(t - 1) * cap;
+  uint32_t* ct = cnt + (size_t)(t - 1) * cap;
+  int cl = 0, cm = 0;
+  uint32_t len = 0;
+#pragma unroll
+  for (int k = 0; k < CM_PPL; ++k) {
+    const bool ok = k < nvalid && l[k] > 0 && (int64_t)l[k] <= Kl && m[k] > 0 && (int64_t)m[k] <= Km;
+    if (len && (!ok || l[k] != cl || m[k] != cm)) { cl_insert(kt, ct, cap - 1, cl, cm, len, status + t); len = 0; }
+    if (ok) { cl = l[k]; cm = m[k]; ++len; }
+  }
+  if (len) cl_insert(kt, ct, cap - 1, cl, cm, len, status + t);
+}
+
 // every table entry: best[cell] = max(count << 32 | ~m): the largest overlap, ties to the smallest m
 __global__ void cl_best_kernel(const u64* __restrict__ keys, const uint32_t* __restrict__ cnt, int64_t entries, uint32_t cap,
                                const int64_t* __restrict__ loff, u64* __restrict__ best) {
@@ -467,6 +510,44 @@ extern "C" int mseg_cell_links(const void* labels, int dtype, int T, int H, int 
     else
       hipLaunchKernelGGL(cl_pairs_kernel<int32_t>, dim3(cl_blocks(lanes)), dim3(CM_BLOCK), 0, st, (const int32_t*)labels, T,
                          HW, label_off, keys, cnt, cap, status);
+    const int64_t entries = (int64_t)(T - 1) * cap;
+    hipLaunchKernelGGL(cl_best_kernel, dim3(cl_blocks(entries)), dim3(CM_BLOCK), 0, st, (const u64*)keys,
+                       (const uint32_t*)cnt, entries, cap, label_off, best);
+  }
+  hipLaunchKernelGGL(cl_out_kernel, dim3(cl_blocks(n_labels)), dim3(CM_BLOCK), 0, st, (const u64*)best, n_labels, pred,
+                     overlap);
+  MSEG_LAUNCH_CHECK();
+  return MSEG_OK;
+}
+
+extern "C" int mseg_cell_links_shifted(const void* labels, int dtype, int T, int H, int W, const int64_t* label_off,
+                                       int64_t n_labels, int64_t table_cap, const int32_t* shift, int32_t* pred,
+                                       int32_t* overlap, int32_t* status, void* ws, size_t ws_bytes, void* stream) {
+  if (!labels || !label_off || !shift || !status || !ws || T <= 0 || H <= 0 || W <= 0 || n_labels < 0) return MSEG_EINVAL;
+  if ((int64_t)H * W >= (1ll << 31) - CM_PPL) return MSEG_EINVAL;
+  if (dtype != MSEG_PIX_U16 && dtype != MSEG_PIX_I32) return MSEG_EINVAL;
+  if (n_labels > 0 && (!pred || !overlap)) return MSEG_EINVAL;
+  const size_t need = mseg_cell_links_workspace_bytes(T, n_labels, table_cap);
+  if (need == 0) return MSEG_EINVAL;
+  if (ws_bytes < need) return MSEG_EWORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  if (hipMemsetAsync(status, 0, sizeof(int32_t) * (size_t)T, st) != hipSuccess) return MSEG_ELAUNCH;
+  if (n_labels == 0) return MSEG_OK;
+  const size_t pairs = (size_t)(T > 1 ? T - 1 : 1);
+  const uint32_t cap = (uint32_t)table_cap;
+  char* b = (char*)ws;
+  u64* keys = (u64*)b;
+  uint32_t* cnt = (uint32_t*)(b + cl_align(pairs * (size_t)cap * sizeof(u64)));
+  u64* best = (u64*)((char*)cnt + cl_align(pairs * (size_t)cap * sizeof(uint32_t)));
+  if (hipMemsetAsync(ws, 0, need, st) != hipSuccess) return MSEG_ELAUNCH;
+  if (T > 1) {
+    const int64_t lanes = (int64_t)(T - 1) * H * (((int64_t)W + CM_PPL - 1) / CM_PPL);
+    if (dtype == MSEG_PIX_U16)
+      hipLaunchKernelGGL(cl_pairs_shifted_kernel<uint16_t>, dim3(cl_blocks(lanes)), dim3(CM_BLOCK), 0, st,
+                         (const uint16_t*)labels, T, H, W, label_off, shift, keys, cnt, cap, status);
+    else
+      hipLaunchKernelGGL(cl_pairs_shifted_kernel<int32_t>, dim3(cl_blocks(lanes)), dim3(CM_BLOCK), 0, st,
+                         (const int32_t*)labels, T, H, W, label_off, shift, keys, cnt, cap, status);
     const int64_t entries = (int64_t)(T - 1) * cap;
     hipLaunchKernelGGL(cl_best_kernel, dim3(cl_blocks(entries)), dim3(CM_BLOCK), 0, st, (const u64*)keys,
                        (const uint32_t*)cnt, entries, cap, label_off, best);

@@ -6,7 +6,10 @@ device (csrc/cells.hip: ``mseg_cell_measure``, ``mseg_cell_links``; DESIGN.md §
 from them here on the host in Python integers and fp64, so the table is exact where it can be and identical from run to
 run.  ``assemble_tracks`` turns the links into track ids: this is OVERLAP linking — a cell follows the cell of the
 previous frame it shares the most pixels with.  There is no motion model and no gap closing: a cell that moves further
-than its own extent between two frames, or that is missed in one frame, starts a new track.
+than its own extent between two frames, or that is missed in one frame, starts a new track.  ``drift=R`` takes the
+usual cause of such jumps out first: the whole field of view moving by a few (tens of) pixels between time points.  The
+integer shift of every frame pair is the peak of the device's foreground-overlap surface (csrc/drift.hip:
+``mseg_stack_drift``), and the links are taken under it (``mseg_cell_links_shifted``).
 """
 import ctypes as C
 import math
@@ -21,15 +24,19 @@ SHAPE_COLUMNS = ['frame', 'label', 'area', 'centroid_y', 'centroid_x', 'bbox_min
                  'bbox_max_col', 'major_axis_length', 'minor_axis_length', 'orientation', 'touches_border']
 CHANNEL_COLUMNS = ['mean_ch{c}', 'std_ch{c}', 'min_ch{c}', 'max_ch{c}', 'sum_ch{c}', 'bg_mean_ch{c}']
 LINK_COLUMNS = ['pred_label', 'overlap', 'track_id', 'parent_track']
+DRIFT_COLUMNS = ['drift_y', 'drift_x', 'centroid_y_reg', 'centroid_x_reg']
+MAX_DRIFT = 128       # largest search radius mseg_stack_drift accepts
 MIN_TABLE = 64        # smallest pair table mseg_cell_links accepts
 
 
-def columns(channels=(), link=True):
-    """the table's columns, in order, for the measured ``channels``"""
+def columns(channels=(), link=True, drift=False):
+    """the table's columns, in order, for the measured ``channels``; ``drift``: with the drift columns (needs ``link``)"""
+    if drift and not link:
+        raise ValueError("the drift columns belong to the link columns: drift needs link")
     cols = list(SHAPE_COLUMNS)
     for c in channels:
         cols += [name.format(c=int(c)) for name in CHANNEL_COLUMNS]
-    return cols + (list(LINK_COLUMNS) if link else [])
+    return cols + (list(LINK_COLUMNS) if link else []) + (list(DRIFT_COLUMNS) if drift else [])
 
 
 def _device(device=None):
@@ -175,7 +182,56 @@ def _pow2(v):
     return 1 << max(int(v) - 1, 0).bit_length()
 
 
-def _links_call(lab, pix, off, cap):
+def check_drift(drift):
+    """the rule of ``measure_cells(drift=...)``, ``InferWorker.drift`` and --drift: None, or an int in 0 .. MAX_DRIFT"""
+    if drift is None:
+        return None
+    if isinstance(drift, bool) or int(drift) != drift or not 0 <= int(drift) <= MAX_DRIFT:
+        raise ValueError(f"drift: None or a whole number of pixels in 0 .. {MAX_DRIFT} expected, got {drift!r}")
+    return int(drift)
+
+
+def drift_raw(lab, pix, off, max_drift):
+    """``mseg_stack_drift`` for the whole stack -> scores uint32 [T - 1, 2R + 1, 2R + 1] on the host: scores[t - 1, dy + R,
+    dx + R] = pixels where the foreground of frame t - 1 moved by (dy, dx) lies on the foreground of frame t"""
+    lib = _lib.load()
+    dev = lab.device
+    T, H, W = (int(v) for v in lab.shape)
+    R = int(max_drift)
+    side = 2 * R + 1
+    off_d = torch.from_numpy(np.ascontiguousarray(off, np.int64)).to(dev)
+    scores = torch.zeros((max(T - 1, 1), side, side), dtype=torch.int32, device=dev)
+    nbytes = lib.mseg_stack_drift_workspace_bytes(T, H, W)
+    if nbytes == 0:
+        raise ValueError(f"mseg_stack_drift: no workspace for a {T} x {H} x {W} stack")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    _lib.check(lib.mseg_stack_drift(lab.data_ptr(), pix, T, H, W, off_d.data_ptr(), R, scores.data_ptr(), ws.data_ptr(),
+                                    ws.numel(), _stream(dev)), "stack_drift")
+    return scores.cpu().numpy().view(np.uint32)[:T - 1]
+
+
+def pick_drift(scores):
+    """scores uint32 [T - 1, 2R + 1, 2R + 1] -> int32 [T, 2] = (dy, dx) of every frame against its predecessor, row 0 =
+    (0, 0).  The largest score wins; ties go to the smallest dy^2 + dx^2, then the smaller dy, then the smaller dx, so a
+    shift that only ties the score at (0, 0) never wins; a pair whose best score is 0 gets (0, 0).  Pure numpy."""
+    scores = np.asarray(scores)
+    if scores.ndim != 3 or scores.shape[1] != scores.shape[2] or scores.shape[1] % 2 == 0:
+        raise ValueError(f"scores: [T - 1, 2R + 1, 2R + 1] expected, got {scores.shape}")
+    R = scores.shape[1] // 2
+    d = np.arange(-R, R + 1, dtype=np.int64)
+    dy, dx = (g.ravel() for g in np.meshgrid(d, d, indexing="ij"))
+    norm = dy * dy + dx * dx
+    shift = np.zeros((scores.shape[0] + 1, 2), np.int32)
+    for t, surface in enumerate(scores, start=1):
+        flat = surface.ravel().astype(np.int64)
+        if flat.max() == 0:
+            continue
+        best = np.lexsort((dx, dy, norm, -flat))[0]            # the last key is the first criterion
+        shift[t] = dy[best], dx[best]
+    return shift
+
+
+def _links_call(lab, pix, off, cap, shift=None):
     lib = _lib.load()
     dev = lab.device
     T, H, W = (int(v) for v in lab.shape)
@@ -188,25 +244,39 @@ def _links_call(lab, pix, off, cap):
     if nbytes == 0:
         raise ValueError(f"mseg_cell_links: no workspace for T = {T}, {n} cells, table {cap}")
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    _lib.check(lib.mseg_cell_links(lab.data_ptr(), pix, T, H, W, off_d.data_ptr(), n, cap, pred.data_ptr(), ovl.data_ptr(),
-                                   status.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)), "cell_links")
+    if shift is None:
+        _lib.check(lib.mseg_cell_links(lab.data_ptr(), pix, T, H, W, off_d.data_ptr(), n, cap, pred.data_ptr(),
+                                       ovl.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)),
+                   "cell_links")
+    else:
+        shift_d = torch.from_numpy(np.ascontiguousarray(shift, np.int32)).to(dev)
+        _lib.check(lib.mseg_cell_links_shifted(lab.data_ptr(), pix, T, H, W, off_d.data_ptr(), n, cap, shift_d.data_ptr(),
+                                               pred.data_ptr(), ovl.data_ptr(), status.data_ptr(), ws.data_ptr(),
+                                               ws.numel(), _stream(dev)), "cell_links_shifted")
     return pred.cpu().numpy()[:n], ovl.cpu().numpy()[:n], status.cpu().numpy()
 
 
-def link_raw(lab, pix, off, table_cap=None):
+def link_raw(lab, pix, off, table_cap=None, shift=None):
     """``mseg_cell_links`` for the whole stack -> (pred int32 [n], overlap int32 [n]) on the host.  The pair tables start
     at 4 entries per cell of the two frames; a frame pair whose table filled up (the device status word says so) is redone
-    on its own with a table of more than H * W entries, which cannot fill up: the result is always exact."""
+    on its own with a table of more than H * W entries, which cannot fill up: the result is always exact.  ``shift``: int32
+    [T, 2] = (dy, dx) per frame against its predecessor (row 0 unused): the links are taken under these shifts
+    (``mseg_cell_links_shifted``); None: same (y, x), as ever."""
     T, H, W = (int(v) for v in lab.shape)
+    if shift is not None:
+        shift = np.ascontiguousarray(shift, np.int32)
+        if shift.shape != (T, 2):
+            raise ValueError(f"shift: int32 [{T}, 2] expected, got {shift.shape}")
     k = np.diff(off)
     if table_cap is None:
         pair = int((k[1:] + k[:-1]).max()) if T > 1 else 0
         table_cap = min(max(MIN_TABLE, _pow2(4 * pair)), _pow2(H * W + 1))
-    pred, ovl, status = _links_call(lab, pix, off, int(table_cap))
+    pred, ovl, status = _links_call(lab, pix, off, int(table_cap), shift)
     pred, ovl = pred.copy(), ovl.copy()
     for t in np.nonzero(status)[0]:
         sub = np.asarray(off[t - 1:t + 2], np.int64) - off[t - 1]
-        p2, o2, s2 = _links_call(lab[t - 1:t + 1], pix, sub, max(MIN_TABLE, _pow2(H * W + 1)))
+        p2, o2, s2 = _links_call(lab[t - 1:t + 1], pix, sub, max(MIN_TABLE, _pow2(H * W + 1)),
+                                 None if shift is None else np.stack([np.zeros(2, np.int32), shift[t]]))
         if s2.any():
             raise RuntimeError("mseg_cell_links: a table of more than H * W entries reported full")
         pred[off[t]:off[t + 1]] = p2[sub[1]:]
@@ -265,12 +335,17 @@ def _axes(n, sy, sx, syy, sxx, sxy):
     return major, minor, orientation
 
 
-def table_from_sums(off, H, W, raw, channels=(), links=None, min_overlap=1):
+def table_from_sums(off, H, W, raw, channels=(), links=None, min_overlap=1, shift=None):
     """the DataFrame from the integer sums of ``measure_raw`` (and ``links`` = (pred, overlap) or None); host arithmetic in
-    Python integers and fp64"""
+    Python integers and fp64.  ``shift``: int [T, 2], the (dy, dx) of every frame against its predecessor the links were
+    taken under (row 0 ignored), or None: with it the table ends with the drift columns"""
     off = np.asarray(off, np.int64)
     area = raw["shape"][0]
-    rows = {c: [] for c in columns(channels, links is not None)}
+    rows = {c: [] for c in columns(channels, links is not None, shift is not None)}
+    if shift is not None:
+        shift = np.asarray(shift, np.int64).reshape(len(off) - 1, 2).copy()
+        shift[0] = 0
+        total = [(int(a), int(b)) for a, b in np.cumsum(shift, axis=0)]      # against frame 0
     sh = [[int(v) for v in plane] for plane in raw["shape"]]
     for t in range(len(off) - 1):
         bg = []
@@ -291,6 +366,8 @@ def table_from_sums(off, H, W, raw, channels=(), links=None, min_overlap=1):
                          int(raw["ch_minmax"][1, ci, s]), sv, bg[ci]]
             if links is not None:
                 vals += [int(links[0][s]), int(links[1][s]), 0, 0]
+            if shift is not None:
+                vals += [total[t][0], total[t][1], sh[1][s] / n - total[t][0], sh[2][s] / n - total[t][1]]
             for c, v in zip(rows, vals):
                 rows[c].append(v)
     df = pd.DataFrame(rows, columns=list(rows))
@@ -301,7 +378,7 @@ def table_from_sums(off, H, W, raw, channels=(), links=None, min_overlap=1):
     return df
 
 
-def measure_cells(mask, img=None, channels=None, link=True, min_overlap=1, device=None):
+def measure_cells(mask, img=None, channels=None, link=True, min_overlap=1, device=None, drift=None):
     """ One row per cell of a segmented stack, ordered by (frame, label).
 
     :param mask: label stack [T, H, W] (or one frame [H, W]): host array or device tensor (int16 holding uint16 bits, or
@@ -312,8 +389,16 @@ def measure_cells(mask, img=None, channels=None, link=True, min_overlap=1, devic
     :param link: add pred_label / overlap (the label of the previous frame sharing the most pixels, ties to the smaller
         label, 0 = none) and track_id / parent_track (``assemble_tracks``).  Overlap linking: no motion model, no gap closing.
     :param min_overlap: links with fewer shared pixels are dropped before the tracks are assembled.
-    :return: pandas.DataFrame with the columns of ``columns(channels, link)``.
+    :param drift: None (default): link at the same (y, x).  R, a whole number in 0 .. 128: take the stage drift out first.
+        Every frame pair gets the integer shift (|dy|, |dx| <= R) under which the foregrounds of the two frames share the
+        most pixels (``pick_drift``), the links are taken under it, and the table ends with drift_y / drift_x (the shift of
+        the frame against frame 0, the same for all its rows) and centroid_y_reg / centroid_x_reg (the centroid minus that
+        shift: a cell that only drifted keeps it).  Whole pixels, translation only; needs ``link``.
+    :return: pandas.DataFrame with the columns of ``columns(channels, link, drift is not None)``.
     """
+    drift = check_drift(drift)
+    if drift is not None and not link:
+        raise ValueError("drift changes how cells are linked: it needs link=True")
     dev = _device(device)
     with torch.cuda.device(dev):
         lab, pix = _labels_to_device(mask, dev)
@@ -331,8 +416,9 @@ def measure_cells(mask, img=None, channels=None, link=True, min_overlap=1, devic
         else:
             channels = []
         raw = measure_raw(lab, pix, off, image, channels)
-        links = link_raw(lab, pix, off) if link else None
-    return table_from_sums(off, H, W, raw, channels, links, min_overlap)
+        shift = pick_drift(drift_raw(lab, pix, off, drift)) if drift is not None else None
+        links = link_raw(lab, pix, off, shift=shift) if link else None
+    return table_from_sums(off, H, W, raw, channels, links, min_overlap, shift)
 
 
 def write_cells(df, csv_path):
