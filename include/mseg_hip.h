@@ -182,7 +182,7 @@ int mseg_first_conv_fwd(const float* x4, const float* w, const float* bias, int 
  *                            first layer does not take the kernel above                                                   */
 #define MSEG_PIX_U8 0
 #define MSEG_PIX_U16 1
-#define MSEG_PIX_I32 2 /* label stacks: mseg_stack_relabel, mseg_cell_measure, mseg_cell_links, mseg_stack_drift */
+#define MSEG_PIX_I32 2 /* label stacks: mseg_stack_relabel, mseg_cell_measure, mseg_cell_links, mseg_stack_drift, mseg_cell_hull */
 #define MSEG_PIX_F32 3 /* mseg_clahe_u16 only: fp32 holding the integers 0..65535 */
 int mseg_frame_minmax(const void* raw, int dtype, size_t npix, uint32_t* minmax, void* stream);
 int mseg_first_conv_fwd_raw(const void* raw, int dtype, int H0, int W0, int pad_top, int pad_left, const uint32_t* minmax,
@@ -589,6 +589,34 @@ int mseg_stack_drift(const void* labels, int dtype, int T, int H, int W, const i
 int mseg_cell_links_shifted(const void* labels, int dtype, int T, int H, int W, const int64_t* label_off, int64_t n_labels,
                             int64_t table_cap, const int32_t* shift, int32_t* pred, int32_t* overlap, int32_t* status,
                             void* ws, size_t ws_bytes, void* stream);
+
+/* ---- per-cell outline measures (csrc/hull.hip) — an extension --------------------------------------------
+ * labels, dtype and label_off as for mseg_cell_links.  A cell is the union of the closed unit squares of its pixels: pixel
+ * (y, x) is the square with the corners (y, x) .. (y + 1, x + 1), so corners are integer points in 0..H x 0..W.  A cell may
+ * be disconnected and may have holes; ids beyond a frame's table and negative ids are not a cell.
+ * mseg_cell_hull: bbox is the device array mseg_cell_measure writes ([n_labels][4] = r0, c0, r1, c1, zeros for absent cells);
+ *   row_off: int64 [n_labels + 1] on the device: cell s owns the corner rows row_off[s] .. row_off[s + 1] - 1 of the
+ *   workspace, r1 - r0 + 1 of them for a present cell and none for an absent one; n_rows = row_off[n_labels].
+ *   out: int64 [10][n_labels], written whole, ten zeros for an absent id:
+ *     0 perimeter   unit edges with a pixel of the cell on one side and a pixel that is not of the cell, or the outside of
+ *                   the frame, on the other (the edges of holes count)
+ *     1 hull_n      vertices of the convex hull of the cell's corners; strict: no three consecutive vertices are collinear
+ *     2 hull_area2  twice the hull's area
+ *     3 feret2      the largest squared distance between two corners
+ *     4 .. 7        ay, ax, by, bx: the pair that attains it, a < b in (y, x) order; of ties the smallest a, then b
+ *     8, 9          minw_num, minw_den2: the smallest caliper width is num / sqrt(den2).  Per hull edge e = (ey, ex) with
+ *                   g = gcd(|ey|, |ex|): num = (largest |cross| of a corner against the edge's line) / g, den2 =
+ *                   (ey^2 + ex^2) / g^2; the edge with the smallest num^2 / den2 wins (compared exactly, in 128 bits),
+ *                   ties to the smaller den2
+ *   status: int32 [1] on the device, written whole.  A pixel of a cell that lies outside the box given for that cell (or
+ *   whose corner rows lie outside the cell's rows) is skipped and sets status[0] != 0: the outputs are then NOT valid; no
+ *   write ever leaves the cell's own rows.  Integers only, int32 / 64-bit atomics: identical bytes from run to run.
+ *   ws >= mseg_cell_hull_workspace_bytes (24 bytes per corner row; 0 = bad arguments).  MSEG_EINVAL: bad sizes, a dtype not
+ *   listed, H * W >= 2^31 - 512; MSEG_EWORKSPACE: ws_bytes too small; nothing is launched on either.  n_labels == 0: status alone. */
+size_t mseg_cell_hull_workspace_bytes(int64_t n_labels, int64_t n_rows);
+int mseg_cell_hull(const void* labels, int dtype, int T, int H, int W, const int64_t* label_off, int64_t n_labels,
+                   const int32_t* bbox, const int64_t* row_off, int64_t n_rows, int64_t* out, int32_t* status, void* ws,
+                   size_t ws_bytes, void* stream);
 
 /* ---- training-set preparation (DataCropWorker src/utils/data_cropping.py:157-264,286,
  * DataImportWorker src/utils/data_import.py:125-194, DataExportWorker src/utils/data_export.py:100-101) -----------------

@@ -10,7 +10,8 @@ the GUI's Export button (inference/result_export.py) for the segmented channel o
 ``--cells`` adds ``mask_<stem>_channel<c>_cells.csv``, one row per cell and frame (inference/cells.py);
 ``--tta K`` segments the average of the predictions of K flipped / rotated copies of every frame (inference/tta.py);
 ``--scale S`` predicts every frame at S times its resolution and segments at its own (inference/resample.py);
-``--drift [R]`` with ``--cells``: cells are linked under the stage drift found within +-R pixels (inference/cells.py).
+``--drift [R]`` with ``--cells``: cells are linked under the stage drift found within +-R pixels (inference/cells.py);
+``--hull`` with ``--cells``: perimeter, convex hull and Feret length / width / angle of every cell (inference/cells.py).
 """
 import argparse
 from pathlib import Path
@@ -82,6 +83,8 @@ class Parser(argparse.ArgumentParser):
                 self.error('--drift needs --cells (it changes how the cell table links frames)')
             if not 0 <= ns.drift <= 128:
                 self.error(f'--drift: a search radius of 0 .. 128 pixels expected, got {ns.drift}')
+        if ns.hull and not ns.cells:
+            self.error('--hull needs --cells (it adds columns to the cell table)')
         if ns.scale != 1:
             if ns.tta > 1:
                 self.error('--scale and --tta > 1 cannot be combined')
@@ -154,6 +157,11 @@ def build_parser():
                              'masks overlap most is found on the device, cells are linked under it, and the table gains '
                              'drift_y / drift_x (the shift against frame 0) and centroid_y_reg / centroid_x_reg.  '
                              'Translation in whole pixels only: no rotation, no scaling, no registered image stack')
+    parser.add_argument('--hull', default=False, action='store_true',
+                        help='[extension] with --cells: add the measures of every cell\'s pixel outline: perimeter (exposed '
+                             'pixel edges), convex_area and solidity, feret_max / feret_min (largest and smallest caliper: '
+                             'the length and width of a rod), feret_angle and the end points of the longest chord.  '
+                             'Computed on the device from the pixel squares: no sub-pixel contour is fitted')
     return parser
 
 
@@ -195,10 +203,13 @@ def main():
     worker.apply_clahe = args.clahe
     worker.min_overlap = args.min_overlap
     worker.drift = args.drift
+    worker.hull = args.hull
     worker.tta = args.tta
     worker.scale = args.scale
     if args.drift is not None:
         print(f'Cell table: linking under the stage drift found within +-{args.drift} px per frame pair')
+    if args.hull:
+        print('Cell table: with the outline measures (perimeter, convex hull, Feret length / width / angle)')
     if args.scale != 1:
         print(f'Inference at {args.scale} x the resolution of the frames')
     if args.tta > 1:

@@ -9,7 +9,9 @@ previous frame it shares the most pixels with.  There is no motion model and no 
 than its own extent between two frames, or that is missed in one frame, starts a new track.  ``drift=R`` takes the
 usual cause of such jumps out first: the whole field of view moving by a few (tens of) pixels between time points.  The
 integer shift of every frame pair is the peak of the device's foreground-overlap surface (csrc/drift.hip:
-``mseg_stack_drift``), and the links are taken under it (``mseg_cell_links_shifted``).
+``mseg_stack_drift``), and the links are taken under it (``mseg_cell_links_shifted``).  ``hull=True`` adds
+the measures of the cell's PIXEL OUTLINE people take from rod-shaped microbes: crack perimeter, convex hull, largest and
+smallest caliper (csrc/hull.hip: ``mseg_cell_hull``).  No sub-pixel contour is fitted.
 """
 import ctypes as C
 import math
@@ -25,18 +27,22 @@ SHAPE_COLUMNS = ['frame', 'label', 'area', 'centroid_y', 'centroid_x', 'bbox_min
 CHANNEL_COLUMNS = ['mean_ch{c}', 'std_ch{c}', 'min_ch{c}', 'max_ch{c}', 'sum_ch{c}', 'bg_mean_ch{c}']
 LINK_COLUMNS = ['pred_label', 'overlap', 'track_id', 'parent_track']
 DRIFT_COLUMNS = ['drift_y', 'drift_x', 'centroid_y_reg', 'centroid_x_reg']
+HULL_COLUMNS = ['perimeter', 'convex_area', 'solidity', 'feret_max', 'feret_min', 'feret_angle', 'feret_y0', 'feret_x0',
+                'feret_y1', 'feret_x1']
 MAX_DRIFT = 128       # largest search radius mseg_stack_drift accepts
 MIN_TABLE = 64        # smallest pair table mseg_cell_links accepts
 
 
-def columns(channels=(), link=True, drift=False):
-    """the table's columns, in order, for the measured ``channels``; ``drift``: with the drift columns (needs ``link``)"""
+def columns(channels=(), link=True, drift=False, hull=False):
+    """the table's columns, in order, for the measured ``channels``; ``drift``: with the drift columns (needs ``link``);
+    ``hull``: with the outline columns, which come last"""
     if drift and not link:
         raise ValueError("the drift columns belong to the link columns: drift needs link")
     cols = list(SHAPE_COLUMNS)
     for c in channels:
         cols += [name.format(c=int(c)) for name in CHANNEL_COLUMNS]
-    return cols + (list(LINK_COLUMNS) if link else []) + (list(DRIFT_COLUMNS) if drift else [])
+    return cols + (list(LINK_COLUMNS) if link else []) + (list(DRIFT_COLUMNS) if drift else []) + \
+        (list(HULL_COLUMNS) if hull else [])
 
 
 def _device(device=None):
@@ -176,6 +182,36 @@ def measure_raw(lab, pix, off, image=None, channels=()):
     for key, parts in out.items():
         res[key] = np.concatenate(parts, axis=2 if key.startswith("bg") else 1) if parts else empty[key]
     return res
+
+
+def hull_raw(lab, pix, off, bbox):
+    """``mseg_cell_hull`` for the whole stack -> int64 [10, n] on the host: perimeter, hull_n, hull_area2, feret2, ay, ax, by,
+    bx, minw_num, minw_den2 per cell slot, zeros for absent ids.  ``bbox``: int32 [n, 4], the boxes of ``measure_raw``; a
+    cell with a pixel outside its box makes the device set its status word, which raises here."""
+    lib = _lib.load()
+    dev = lab.device
+    T, H, W = (int(v) for v in lab.shape)
+    n = int(off[-1])
+    bbox = np.ascontiguousarray(bbox, np.int32).reshape(n, 4)
+    row_off = np.zeros(n + 1, np.int64)        # corner rows of a present cell: r1 - r0 + 1; an absent one (r1 == 0) has none
+    np.cumsum(np.where(bbox[:, 2] > bbox[:, 0], bbox[:, 2].astype(np.int64) - bbox[:, 0] + 1, 0), out=row_off[1:])
+    n_rows = int(row_off[-1])
+    if n == 0:
+        return np.zeros((10, 0), np.int64)
+    off_d = torch.from_numpy(np.ascontiguousarray(off, np.int64)).to(dev)
+    bbox_d, row_d = torch.from_numpy(bbox).to(dev), torch.from_numpy(row_off).to(dev)
+    out = torch.zeros(10 * n + 1, dtype=torch.int64, device=dev)      # the last element holds the status word: one download
+    nbytes = lib.mseg_cell_hull_workspace_bytes(n, n_rows)
+    if nbytes == 0:
+        raise ValueError(f"mseg_cell_hull: no workspace for {n} cells with {n_rows} rows")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    _lib.check(lib.mseg_cell_hull(lab.data_ptr(), pix, T, H, W, off_d.data_ptr(), n, bbox_d.data_ptr(), row_d.data_ptr(),
+                                  n_rows, out.data_ptr(), out.data_ptr() + 80 * n, ws.data_ptr(), ws.numel(), _stream(dev)),
+               "cell_hull")
+    host = out.cpu().numpy()
+    if host[-1:].view(np.int32)[0] != 0:
+        raise RuntimeError("mseg_cell_hull: a cell has pixels outside the bounding box given for it")
+    return host[:-1].reshape(10, n)
 
 
 def _pow2(v):
@@ -335,13 +371,26 @@ def _axes(n, sy, sx, syy, sxx, sxy):
     return major, minor, orientation
 
 
-def table_from_sums(off, H, W, raw, channels=(), links=None, min_overlap=1, shift=None):
+def _outline(area, h):
+    """the outline columns of one cell from its area and the ten integers of ``mseg_cell_hull`` (HULL_COLUMNS order)"""
+    per, _, area2, feret2, ay, ax, by, bx, num, den2 = h
+    convex = area2 / 2
+    return [per, convex, area / convex, math.sqrt(feret2), num / math.sqrt(den2), math.atan2(bx - ax, by - ay), ay, ax, by,
+            bx]
+
+
+def table_from_sums(off, H, W, raw, channels=(), links=None, min_overlap=1, shift=None, hull=None):
     """the DataFrame from the integer sums of ``measure_raw`` (and ``links`` = (pred, overlap) or None); host arithmetic in
     Python integers and fp64.  ``shift``: int [T, 2], the (dy, dx) of every frame against its predecessor the links were
-    taken under (row 0 ignored), or None: with it the table ends with the drift columns"""
+    taken under (row 0 ignored), or None: with it the drift columns follow the link columns.  ``hull``: int [10, n], the
+    integers of ``hull_raw``, or None: with it the table ends with the outline columns: perimeter (exposed pixel edges),
+    convex_area = hull_area2 / 2, solidity = area / convex_area, feret_max = sqrt(feret2), feret_min = num / sqrt(den2),
+    feret_angle = atan2(bx - ax, by - ay) in (-pi/2, pi/2] from the row axis, and the chord's end points"""
     off = np.asarray(off, np.int64)
     area = raw["shape"][0]
-    rows = {c: [] for c in columns(channels, links is not None, shift is not None)}
+    rows = {c: [] for c in columns(channels, links is not None, shift is not None, hull is not None)}
+    if hull is not None:
+        hl = [[int(v) for v in plane] for plane in np.asarray(hull).reshape(10, len(area))]
     if shift is not None:
         shift = np.asarray(shift, np.int64).reshape(len(off) - 1, 2).copy()
         shift[0] = 0
@@ -368,6 +417,8 @@ def table_from_sums(off, H, W, raw, channels=(), links=None, min_overlap=1, shif
                 vals += [int(links[0][s]), int(links[1][s]), 0, 0]
             if shift is not None:
                 vals += [total[t][0], total[t][1], sh[1][s] / n - total[t][0], sh[2][s] / n - total[t][1]]
+            if hull is not None:
+                vals += _outline(n, [plane[s] for plane in hl])
             for c, v in zip(rows, vals):
                 rows[c].append(v)
     df = pd.DataFrame(rows, columns=list(rows))
@@ -378,7 +429,7 @@ def table_from_sums(off, H, W, raw, channels=(), links=None, min_overlap=1, shif
     return df
 
 
-def measure_cells(mask, img=None, channels=None, link=True, min_overlap=1, device=None, drift=None):
+def measure_cells(mask, img=None, channels=None, link=True, min_overlap=1, device=None, drift=None, hull=False):
     """ One row per cell of a segmented stack, ordered by (frame, label).
 
     :param mask: label stack [T, H, W] (or one frame [H, W]): host array or device tensor (int16 holding uint16 bits, or
@@ -394,7 +445,11 @@ def measure_cells(mask, img=None, channels=None, link=True, min_overlap=1, devic
         most pixels (``pick_drift``), the links are taken under it, and the table ends with drift_y / drift_x (the shift of
         the frame against frame 0, the same for all its rows) and centroid_y_reg / centroid_x_reg (the centroid minus that
         shift: a cell that only drifted keeps it).  Whole pixels, translation only; needs ``link``.
-    :return: pandas.DataFrame with the columns of ``columns(channels, link, drift is not None)``.
+    :param hull: True: the table ends with the measures of every cell's pixel outline (HULL_COLUMNS): the crack perimeter,
+        the area of the convex hull of the pixel corners and the solidity, the largest caliper (Feret diameter) with its
+        angle and end points, and the smallest caliper.  The cell is the union of its pixel squares: no sub-pixel contour
+        is fitted, a slanted edge's perimeter is overestimated by up to sqrt(2).  Does not need ``link``.
+    :return: pandas.DataFrame with the columns of ``columns(channels, link, drift is not None, hull)``.
     """
     drift = check_drift(drift)
     if drift is not None and not link:
@@ -418,7 +473,8 @@ def measure_cells(mask, img=None, channels=None, link=True, min_overlap=1, devic
         raw = measure_raw(lab, pix, off, image, channels)
         shift = pick_drift(drift_raw(lab, pix, off, drift)) if drift is not None else None
         links = link_raw(lab, pix, off, shift=shift) if link else None
-    return table_from_sums(off, H, W, raw, channels, links, min_overlap, shift)
+        outline = hull_raw(lab, pix, off, raw["bbox"]) if hull else None
+    return table_from_sums(off, H, W, raw, channels, links, min_overlap, shift, outline)
 
 
 def write_cells(df, csv_path):

@@ -96,6 +96,9 @@ class InferWorker(QObject):
     # [extension] cell_table: None = link at the same (y, x); R = 0 .. 128: estimate the stage drift of every frame pair
     # within +-R pixels on the device and link under it (inference/cells.py)
     drift = None
+    # [extension] cell_table: True = the table ends with the outline measures of every cell (perimeter, convex hull, Feret
+    # length / width / angle; inference/cells.py)
+    hull = False
     # [extension] test-time augmentation (inference/tta.py): 1 = off (no existing route changes), 2 / 4 / 8 =
     # every frame is predicted under that many flips / rotations, the predictions are mapped back and averaged (fp32, in
     # member order) and the average is segmented: K network forwards per frame.  Whole-frame inference only
@@ -873,9 +876,11 @@ class InferWorker(QObject):
         """ [extension] The per-cell table of a segmented stack (inference/cells.py ``measure_cells``): ``results`` are the
         masks of ``infer_stack``, ``img`` the [T, C, H, W] image (a strided view is read in place) whose ``channels``
         (numbers of the source image, they name the columns) are measured.  Overlap linking: no motion model, no gap
-        closing; with ``self.drift`` set, under the estimated stage drift of every frame pair. """
+        closing; with ``self.drift`` set, under the estimated stage drift of every frame pair; with ``self.hull`` set, with
+        the outline columns. """
         from .cells import measure_cells
-        df = measure_cells(results, img, link=True, min_overlap=self.min_overlap, device=self.device, drift=self.drift)
+        df = measure_cells(results, img, link=True, min_overlap=self.min_overlap, device=self.device, drift=self.drift,
+                           hull=self.hull)
         if img is not None and channels is not None:      # the view holds the chosen channels only: name them by source
             names = {f'{k}_ch{i}': f'{k}_ch{int(c)}' for i, c in reversed(list(enumerate(channels)))
                      for k in ('mean', 'std', 'min', 'max', 'sum', 'bg_mean')}
