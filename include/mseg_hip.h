@@ -182,7 +182,7 @@ int mseg_first_conv_fwd(const float* x4, const float* w, const float* bias, int 
  *                            first layer does not take the kernel above                                                   */
 #define MSEG_PIX_U8 0
 #define MSEG_PIX_U16 1
-#define MSEG_PIX_I32 2 /* label stacks: mseg_stack_relabel, mseg_cell_measure, mseg_cell_links, mseg_stack_drift, mseg_cell_hull */
+#define MSEG_PIX_I32 2 /* label stacks: mseg_stack_relabel, mseg_cell_measure, mseg_cell_links, mseg_stack_drift, mseg_cell_hull, mseg_cell_midline */
 #define MSEG_PIX_F32 3 /* mseg_clahe_u16 only: fp32 holding the integers 0..65535 */
 int mseg_frame_minmax(const void* raw, int dtype, size_t npix, uint32_t* minmax, void* stream);
 int mseg_first_conv_fwd_raw(const void* raw, int dtype, int H0, int W0, int pad_top, int pad_left, const uint32_t* minmax,
@@ -617,6 +617,46 @@ size_t mseg_cell_hull_workspace_bytes(int64_t n_labels, int64_t n_rows);
 int mseg_cell_hull(const void* labels, int dtype, int T, int H, int W, const int64_t* label_off, int64_t n_labels,
                    const int32_t* bbox, const int64_t* row_off, int64_t n_rows, int64_t* out, int32_t* status, void* ws,
                    size_t ws_bytes, void* stream);
+
+/* ---- per-cell midline (csrc/midline.hip) — an extension --------------------------------------------------
+ * labels, dtype and label_off as for mseg_cell_links.  A cell is the set of pixels of frame t whose id is l, 1 <= l <= K_t.
+ * Ids beyond the frame's table and negative ids are not a cell, neither as a pixel nor as a neighbour; nor are the pixels of
+ * other cells or anything outside the frame.  Every cell is thinned ALONE: two touching cells do not see each other.
+ * Thinning: Guo & Hall 1989, algorithm A1, fully parallel, two sub-passes.  The neighbours of p = (y, x), clockwise from
+ * north: P2 = (y-1, x), P3 = (y-1, x+1), P4 = (y, x+1), P5 = (y+1, x+1), P6 = (y+1, x), P7 = (y+1, x-1), P8 = (y, x-1),
+ * P9 = (y-1, x-1); each is 1 if that pixel belongs to the cell in the current state, else 0.
+ *   C  = (!P2 & (P3 | P4)) + (!P4 & (P5 | P6)) + (!P6 & (P7 | P8)) + (!P8 & (P9 | P2))
+ *   N1 = (P9 | P2) + (P3 | P4) + (P5 | P6) + (P7 | P8),  N2 = (P2 | P3) + (P4 | P5) + (P6 | P7) + (P8 | P9),  N = min(N1, N2)
+ *   m0 = (P6 | P7 | !P9) & P8 for sub-pass 0,  m1 = (P2 | P3 | !P5) & P4 for sub-pass 1
+ * Sub-pass k deletes every pixel of the cell with C == 1, 2 <= N <= 3 and m_k == 0; all decisions of a sub-pass are taken on
+ * the state before it.  A round is sub-pass 0 followed by sub-pass 1; rounds repeat until a whole round deletes nothing.
+ * mseg_cell_midline: bbox as for mseg_cell_hull ([n_labels][4] = r0, c0, r1, c1 with r1, c1 exclusive, zeros for absent
+ *   cells).  Cell s owns a bitmap of (r1 - r0 + 2) rows of ceil((c1 - c0 + 2) / 64) 64-bit words (the box and a ring of one
+ *   empty pixel) in each of the two buffers of the workspace; word_off: int64 [n_labels + 1] on the device, the cumulative sum
+ *   of these word counts, none for an absent cell; n_words = word_off[n_labels].
+ *   out: int64 [12][n_labels], written whole, twelve zeros for an absent id; S = the surviving pixels of the cell:
+ *     0 skel_n     |S|
+ *     1 n_orth     unordered pairs of S that are 4-neighbours
+ *     2 n_diag     unordered pairs of S that are diagonal neighbours and whose two common 4-neighbours are both not in S
+ *     3 n_end      pixels of S with exactly one 8-neighbour in S
+ *     4 n_branch   pixels of S whose crossing number (0 -> 1 steps in P2, P3, ..., P9, P2, taken on S) is >= 3
+ *     5 rounds     rounds run, the last, empty one included (a one-pixel cell: 1)
+ *     6, 7, 8      e0_y, e0_x, e0_d2: the first end point in (y, x) order, and the squared distance from its centre to the
+ *                  centre of the nearest position that is not of the cell; rows -1 and H and columns -1 and W count as such
+ *     9, 10, 11    e1_y, e1_x, e1_d2: the last end point in (y, x) order, likewise
+ *   skel_n == 1: that pixel is e0 and e1 (n_end stays 0); n_end == 1: e0 == e1; n_end == 0 and skel_n > 1: planes 6 .. 11 are 0.
+ *   skeleton: uint8 [T][H][W] on the device or NULL; written whole: 1 on S of every cell, 0 elsewhere.
+ *   status: int32 [1] on the device, written whole.  Bit 0: a pixel of a cell lies outside the box given for it (or the
+ *   cell's box and words do not fit each other or the frame): it is skipped, and no write leaves the cell's own words.
+ *   Bit 1: a cell was still changing after (r1 - r0) + (c1 - c0) + 2 rounds, the cap that bounds the loop; a correct build
+ *   never reaches it.  With either bit set the outputs are NOT valid.  Integers only, order-free integer atomics: identical
+ *   bytes from run to run.  ws >= mseg_cell_midline_workspace_bytes (16 bytes per word, each buffer rounded up to 256 bytes; 0 =
+ *   bad arguments).  MSEG_EINVAL: bad sizes, a dtype not listed, H * W >= 2^31 - 512; MSEG_EWORKSPACE: ws_bytes too small;
+ *   nothing is launched and nothing written on either.  n_labels == 0: status (and skeleton, if given) alone.            */
+size_t mseg_cell_midline_workspace_bytes(int64_t n_labels, int64_t n_words);
+int mseg_cell_midline(const void* labels, int dtype, int T, int H, int W, const int64_t* label_off, int64_t n_labels,
+                      const int32_t* bbox, const int64_t* word_off, int64_t n_words, int64_t* out, uint8_t* skeleton,
+                      int32_t* status, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- training-set preparation (DataCropWorker src/utils/data_cropping.py:157-264,286,
  * DataImportWorker src/utils/data_import.py:125-194, DataExportWorker src/utils/data_export.py:100-101) -----------------

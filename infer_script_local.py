@@ -11,7 +11,8 @@ the GUI's Export button (inference/result_export.py) for the segmented channel o
 ``--tta K`` segments the average of the predictions of K flipped / rotated copies of every frame (inference/tta.py);
 ``--scale S`` predicts every frame at S times its resolution and segments at its own (inference/resample.py);
 ``--drift [R]`` with ``--cells``: cells are linked under the stage drift found within +-R pixels (inference/cells.py);
-``--hull`` with ``--cells``: perimeter, convex hull and Feret length / width / angle of every cell (inference/cells.py).
+``--hull`` with ``--cells``: perimeter, convex hull and Feret length / width / angle of every cell (inference/cells.py);
+``--midline`` with ``--cells``: the thinned midline of every cell: its length, for bent and filamentous cells (inference/cells.py).
 """
 import argparse
 from pathlib import Path
@@ -85,6 +86,8 @@ class Parser(argparse.ArgumentParser):
                 self.error(f'--drift: a search radius of 0 .. 128 pixels expected, got {ns.drift}')
         if ns.hull and not ns.cells:
             self.error('--hull needs --cells (it adds columns to the cell table)')
+        if ns.midline and not ns.cells:
+            self.error('--midline needs --cells (it adds columns to the cell table)')
         if ns.scale != 1:
             if ns.tta > 1:
                 self.error('--scale and --tta > 1 cannot be combined')
@@ -162,6 +165,13 @@ def build_parser():
                              'pixel edges), convex_area and solidity, feret_max / feret_min (largest and smallest caliper: '
                              'the length and width of a rod), feret_angle and the end points of the longest chord.  '
                              'Computed on the device from the pixel squares: no sub-pixel contour is fitted')
+    parser.add_argument('--midline', default=False, action='store_true',
+                        help='[extension] with --cells: thin every cell to its one-pixel skeleton on the device (Guo-Hall) and '
+                             'add skeleton_pixels / skeleton_length / skeleton_ends / skeleton_branches, midline_length (the '
+                             'skeleton\'s chain length extended to the cell\'s edge at both ends: the length of a bent or '
+                             'filamentous cell, where feret_max is only its chord; NaN for branched or ring skeletons), '
+                             'midline_width = area / midline_length and the two end points.  Whole pixels: no pruning, no '
+                             'sub-pixel midline; for straight rods feret_max (--hull) is the better length')
     return parser
 
 
@@ -204,12 +214,15 @@ def main():
     worker.min_overlap = args.min_overlap
     worker.drift = args.drift
     worker.hull = args.hull
+    worker.midline = args.midline
     worker.tta = args.tta
     worker.scale = args.scale
     if args.drift is not None:
         print(f'Cell table: linking under the stage drift found within +-{args.drift} px per frame pair')
     if args.hull:
         print('Cell table: with the outline measures (perimeter, convex hull, Feret length / width / angle)')
+    if args.midline:
+        print('Cell table: with the midline measures (thinned skeleton, midline length / width, end points)')
     if args.scale != 1:
         print(f'Inference at {args.scale} x the resolution of the frames')
     if args.tta > 1:

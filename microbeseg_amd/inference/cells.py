@@ -11,7 +11,10 @@ usual cause of such jumps out first: the whole field of view moving by a few (te
 integer shift of every frame pair is the peak of the device's foreground-overlap surface (csrc/drift.hip:
 ``mseg_stack_drift``), and the links are taken under it (``mseg_cell_links_shifted``).  ``hull=True`` adds
 the measures of the cell's PIXEL OUTLINE people take from rod-shaped microbes: crack perimeter, convex hull, largest and
-smallest caliper (csrc/hull.hip: ``mseg_cell_hull``).  No sub-pixel contour is fitted.
+smallest caliper (csrc/hull.hip: ``mseg_cell_hull``).  No sub-pixel contour is fitted.  ``midline=True`` adds the
+length along a BENT cell, where the largest caliper is only the chord: every cell is thinned alone to a one-pixel skeleton
+(Guo & Hall) and the skeleton is counted (csrc/midline.hip: ``mseg_cell_midline``).  Whole pixels: no
+pruning, no sub-pixel midline; for straight rods the caliper stays the better length.
 """
 import ctypes as C
 import math
@@ -29,20 +32,22 @@ LINK_COLUMNS = ['pred_label', 'overlap', 'track_id', 'parent_track']
 DRIFT_COLUMNS = ['drift_y', 'drift_x', 'centroid_y_reg', 'centroid_x_reg']
 HULL_COLUMNS = ['perimeter', 'convex_area', 'solidity', 'feret_max', 'feret_min', 'feret_angle', 'feret_y0', 'feret_x0',
                 'feret_y1', 'feret_x1']
+MIDLINE_COLUMNS = ['skeleton_pixels', 'skeleton_length', 'skeleton_ends', 'skeleton_branches', 'midline_length',
+                   'midline_width', 'midline_y0', 'midline_x0', 'midline_y1', 'midline_x1']
 MAX_DRIFT = 128       # largest search radius mseg_stack_drift accepts
 MIN_TABLE = 64        # smallest pair table mseg_cell_links accepts
 
 
-def columns(channels=(), link=True, drift=False, hull=False):
+def columns(channels=(), link=True, drift=False, hull=False, midline=False):
     """the table's columns, in order, for the measured ``channels``; ``drift``: with the drift columns (needs ``link``);
-    ``hull``: with the outline columns, which come last"""
+    ``hull``: with the outline columns; ``midline``: with the midline columns, which come last"""
     if drift and not link:
         raise ValueError("the drift columns belong to the link columns: drift needs link")
     cols = list(SHAPE_COLUMNS)
     for c in channels:
         cols += [name.format(c=int(c)) for name in CHANNEL_COLUMNS]
     return cols + (list(LINK_COLUMNS) if link else []) + (list(DRIFT_COLUMNS) if drift else []) + \
-        (list(HULL_COLUMNS) if hull else [])
+        (list(HULL_COLUMNS) if hull else []) + (list(MIDLINE_COLUMNS) if midline else [])
 
 
 def _device(device=None):
@@ -214,6 +219,43 @@ def hull_raw(lab, pix, off, bbox):
     return host[:-1].reshape(10, n)
 
 
+def midline_raw(lab, pix, off, bbox, skeleton=False):
+    """``mseg_cell_midline`` for the whole stack -> int64 [12, n] on the host: skel_n, n_orth, n_diag, n_end, n_branch, rounds,
+    e0_y, e0_x, e0_d2, e1_y, e1_x, e1_d2 per cell slot, zeros for absent ids; with ``skeleton`` also the uint8 [T, H, W] image
+    of all skeletons.  ``bbox``: int32 [n, 4], the boxes of ``measure_raw``.  A set status word raises."""
+    lib = _lib.load()
+    dev = lab.device
+    T, H, W = (int(v) for v in lab.shape)
+    n = int(off[-1])
+    bbox = np.ascontiguousarray(bbox, np.int32).reshape(n, 4)
+    b = bbox.astype(np.int64)
+    word_off = np.zeros(n + 1, np.int64)       # bit rows of a present cell: the box and a ring of one pixel, rows of 64-bit words
+    np.cumsum(np.where(b[:, 2] > b[:, 0], (b[:, 2] - b[:, 0] + 2) * ((b[:, 3] - b[:, 1] + 2 + 63) // 64), 0), out=word_off[1:])
+    n_words = int(word_off[-1])
+    if n == 0:
+        ints = np.zeros((12, 0), np.int64)
+        return (ints, np.zeros((T, H, W), np.uint8)) if skeleton else ints
+    skel = torch.empty((T, H, W), dtype=torch.uint8, device=dev) if skeleton else None
+    off_d = torch.from_numpy(np.ascontiguousarray(off, np.int64)).to(dev)
+    bbox_d, word_d = torch.from_numpy(bbox).to(dev), torch.from_numpy(word_off).to(dev)
+    out = torch.zeros(12 * n + 1, dtype=torch.int64, device=dev)      # the last element holds the status word: one download
+    nbytes = lib.mseg_cell_midline_workspace_bytes(n, n_words)
+    if nbytes == 0:
+        raise ValueError(f"mseg_cell_midline: no workspace for {n} cells with {n_words} words")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    _lib.check(lib.mseg_cell_midline(lab.data_ptr(), pix, T, H, W, off_d.data_ptr(), n, bbox_d.data_ptr(), word_d.data_ptr(),
+                                     n_words, out.data_ptr(), skel.data_ptr() if skeleton else None, out.data_ptr() + 96 * n,
+                                     ws.data_ptr(), ws.numel(), _stream(dev)), "cell_midline")
+    host = out.cpu().numpy()
+    status = int(host[-1:].view(np.int32)[0])
+    if status & 1:
+        raise RuntimeError("mseg_cell_midline: a cell has pixels outside the bounding box given for it")
+    if status:
+        raise RuntimeError("mseg_cell_midline: a cell was still being thinned at the round cap")
+    ints = host[:-1].reshape(12, n)
+    return (ints, skel.cpu().numpy()) if skeleton else ints
+
+
 def _pow2(v):
     return 1 << max(int(v) - 1, 0).bit_length()
 
@@ -379,18 +421,35 @@ def _outline(area, h):
             bx]
 
 
-def table_from_sums(off, H, W, raw, channels=(), links=None, min_overlap=1, shift=None, hull=None):
+def _midline(area, m):
+    """the midline columns of one cell from its area and the twelve integers of ``mseg_cell_midline`` (MIDLINE_COLUMNS order)"""
+    skel_n, n_orth, n_diag, n_end, n_branch, _, y0, x0, d0, y1, x1, d1 = m
+    chain = n_orth + math.sqrt(2.0) * n_diag
+    if (n_end == 2 and n_branch == 0) or skel_n == 1:
+        length = chain + math.sqrt(d0) + math.sqrt(d1) - 1      # centre-to-centre at both ends -> centre-to-edge
+    else:
+        length = float("nan")                                   # a ring or a branched skeleton has no single midline
+    return [skel_n, chain, n_end, n_branch, length, area / length, y0, x0, y1, x1]
+
+
+def table_from_sums(off, H, W, raw, channels=(), links=None, min_overlap=1, shift=None, hull=None, midline=None):
     """the DataFrame from the integer sums of ``measure_raw`` (and ``links`` = (pred, overlap) or None); host arithmetic in
     Python integers and fp64.  ``shift``: int [T, 2], the (dy, dx) of every frame against its predecessor the links were
     taken under (row 0 ignored), or None: with it the drift columns follow the link columns.  ``hull``: int [10, n], the
     integers of ``hull_raw``, or None: with it the table ends with the outline columns: perimeter (exposed pixel edges),
     convex_area = hull_area2 / 2, solidity = area / convex_area, feret_max = sqrt(feret2), feret_min = num / sqrt(den2),
-    feret_angle = atan2(bx - ax, by - ay) in (-pi/2, pi/2] from the row axis, and the chord's end points"""
+    feret_angle = atan2(bx - ax, by - ay) in (-pi/2, pi/2] from the row axis, and the chord's end points.  ``midline``: int
+    [12, n], the integers of ``midline_raw``, or None: with it the table ends with the midline columns: skeleton_pixels =
+    skel_n, skeleton_length = n_orth + sqrt(2) n_diag, skeleton_ends, skeleton_branches, midline_length = skeleton_length +
+    sqrt(e0_d2) + sqrt(e1_d2) - 1 where the skeleton is one open chain (n_end == 2 and n_branch == 0) or one pixel, NaN
+    otherwise, midline_width = area / midline_length, and the two end points (0 where there are none)"""
     off = np.asarray(off, np.int64)
     area = raw["shape"][0]
-    rows = {c: [] for c in columns(channels, links is not None, shift is not None, hull is not None)}
+    rows = {c: [] for c in columns(channels, links is not None, shift is not None, hull is not None, midline is not None)}
     if hull is not None:
         hl = [[int(v) for v in plane] for plane in np.asarray(hull).reshape(10, len(area))]
+    if midline is not None:
+        ml = [[int(v) for v in plane] for plane in np.asarray(midline).reshape(12, len(area))]
     if shift is not None:
         shift = np.asarray(shift, np.int64).reshape(len(off) - 1, 2).copy()
         shift[0] = 0
@@ -419,6 +478,8 @@ def table_from_sums(off, H, W, raw, channels=(), links=None, min_overlap=1, shif
                 vals += [total[t][0], total[t][1], sh[1][s] / n - total[t][0], sh[2][s] / n - total[t][1]]
             if hull is not None:
                 vals += _outline(n, [plane[s] for plane in hl])
+            if midline is not None:
+                vals += _midline(n, [plane[s] for plane in ml])
             for c, v in zip(rows, vals):
                 rows[c].append(v)
     df = pd.DataFrame(rows, columns=list(rows))
@@ -429,7 +490,8 @@ def table_from_sums(off, H, W, raw, channels=(), links=None, min_overlap=1, shif
     return df
 
 
-def measure_cells(mask, img=None, channels=None, link=True, min_overlap=1, device=None, drift=None, hull=False):
+def measure_cells(mask, img=None, channels=None, link=True, min_overlap=1, device=None, drift=None, hull=False,
+                  midline=False):
     """ One row per cell of a segmented stack, ordered by (frame, label).
 
     :param mask: label stack [T, H, W] (or one frame [H, W]): host array or device tensor (int16 holding uint16 bits, or
@@ -449,7 +511,14 @@ def measure_cells(mask, img=None, channels=None, link=True, min_overlap=1, devic
         the area of the convex hull of the pixel corners and the solidity, the largest caliper (Feret diameter) with its
         angle and end points, and the smallest caliper.  The cell is the union of its pixel squares: no sub-pixel contour
         is fitted, a slanted edge's perimeter is overestimated by up to sqrt(2).  Does not need ``link``.
-    :return: pandas.DataFrame with the columns of ``columns(channels, link, drift is not None, hull)``.
+    :param midline: True: the table ends with the measures of every cell's skeleton (MIDLINE_COLUMNS).  Every cell is thinned
+        alone to a one-pixel skeleton (Guo & Hall 1989) on the device; skeleton_length is its chain length (1 per step
+        along a row or column, sqrt(2) per diagonal step), midline_length extends it at both end points to the cell's edge:
+        the length of a bent or filamentous cell, where feret_max is only the chord.  NaN for a ring or a branched skeleton
+        (skeleton_ends / skeleton_branches say which; boundary noise can branch a skeleton, nothing is pruned).  Chain
+        lengths depend on the direction (about -11 % at 45 degrees): for straight rods feret_max is the better length, for
+        round cells the midline means nothing.  Needs neither ``link`` nor ``hull``.
+    :return: pandas.DataFrame with the columns of ``columns(channels, link, drift is not None, hull, midline)``.
     """
     drift = check_drift(drift)
     if drift is not None and not link:
@@ -474,7 +543,8 @@ def measure_cells(mask, img=None, channels=None, link=True, min_overlap=1, devic
         shift = pick_drift(drift_raw(lab, pix, off, drift)) if drift is not None else None
         links = link_raw(lab, pix, off, shift=shift) if link else None
         outline = hull_raw(lab, pix, off, raw["bbox"]) if hull else None
-    return table_from_sums(off, H, W, raw, channels, links, min_overlap, shift, outline)
+        skel = midline_raw(lab, pix, off, raw["bbox"]) if midline else None
+    return table_from_sums(off, H, W, raw, channels, links, min_overlap, shift, outline, skel)
 
 
 def write_cells(df, csv_path):

@@ -99,6 +99,9 @@ class InferWorker(QObject):
     # [extension] cell_table: True = the table ends with the outline measures of every cell (perimeter, convex hull, Feret
     # length / width / angle; inference/cells.py)
     hull = False
+    # [extension] cell_table: True = the table ends with the midline measures of every cell (the cell thinned to its
+    # skeleton on the device; skeleton and midline length, end points; inference/cells.py)
+    midline = False
     # [extension] test-time augmentation (inference/tta.py): 1 = off (no existing route changes), 2 / 4 / 8 =
     # every frame is predicted under that many flips / rotations, the predictions are mapped back and averaged (fp32, in
     # member order) and the average is segmented: K network forwards per frame.  Whole-frame inference only
@@ -877,10 +880,10 @@ class InferWorker(QObject):
         masks of ``infer_stack``, ``img`` the [T, C, H, W] image (a strided view is read in place) whose ``channels``
         (numbers of the source image, they name the columns) are measured.  Overlap linking: no motion model, no gap
         closing; with ``self.drift`` set, under the estimated stage drift of every frame pair; with ``self.hull`` set, with
-        the outline columns. """
+        the outline columns; with ``self.midline`` set, with the midline columns. """
         from .cells import measure_cells
         df = measure_cells(results, img, link=True, min_overlap=self.min_overlap, device=self.device, drift=self.drift,
-                           hull=self.hull)
+                           hull=self.hull, midline=self.midline)
         if img is not None and channels is not None:      # the view holds the chosen channels only: name them by source
             names = {f'{k}_ch{i}': f'{k}_ch{int(c)}' for i, c in reversed(list(enumerate(channels)))
                      for k in ('mean', 'std', 'min', 'max', 'sum', 'bg_mean')}
