@@ -182,7 +182,7 @@ int mseg_first_conv_fwd(const float* x4, const float* w, const float* bias, int 
  *                            first layer does not take the kernel above                                                   */
 #define MSEG_PIX_U8 0
 #define MSEG_PIX_U16 1
-#define MSEG_PIX_I32 2 /* label stacks: mseg_stack_relabel, mseg_cell_measure, mseg_cell_links, mseg_stack_drift, mseg_cell_hull, mseg_cell_midline */
+#define MSEG_PIX_I32 2 /* label stacks: mseg_stack_relabel, mseg_cell_measure, mseg_cell_links, mseg_stack_drift, mseg_cell_hull, mseg_cell_midline, mseg_cell_order_stats */
 #define MSEG_PIX_F32 3 /* mseg_clahe_u16 only: fp32 holding the integers 0..65535 */
 int mseg_frame_minmax(const void* raw, int dtype, size_t npix, uint32_t* minmax, void* stream);
 int mseg_first_conv_fwd_raw(const void* raw, int dtype, int H0, int W0, int pad_top, int pad_left, const uint32_t* minmax,
@@ -657,6 +657,34 @@ size_t mseg_cell_midline_workspace_bytes(int64_t n_labels, int64_t n_words);
 int mseg_cell_midline(const void* labels, int dtype, int T, int H, int W, const int64_t* label_off, int64_t n_labels,
                       const int32_t* bbox, const int64_t* word_off, int64_t n_words, int64_t* out, uint8_t* skeleton,
                       int32_t* status, void* ws, size_t ws_bytes, void* stream);
+
+/* ---- per-cell order statistics (csrc/order_stats.hip) — an extension --------------------------------------
+ * labels, label_dtype, label_off, img, img_dtype and the four element strides as for mseg_cell_measure: the image is uint8
+ * or uint16 and is read in place, whatever its strides.  Ids beyond a frame's table and negative ids are neither cell nor
+ * background.  bbox is the device array mseg_cell_measure writes ([n_labels][4] = r0, c0, r1, c1, half-open, zeros for an
+ * absent cell).  1 <= R <= 16, 1 <= C.  ranks: int64 [R][n_labels] on the device, bg_ranks: int64 [R][T]; ranks count from 0.
+ * mseg_cell_order_stats: outputs, written whole, integers only, identical bytes from run to run:
+ *     values     uint32 [R][C][n_labels]  values[j][c][s] = the element of rank ranks[j][s] in the ascending multiset of the
+ *                                         channel-c values of the pixels of cell s that lie inside its box
+ *     bg_values  uint32 [R][T][C]         the same for the label-0 pixels of frame t and bg_ranks[j][t]
+ *   An absent cell (an all-zero box) and a frame without background pixels get zeros; their ranks are not read as ranks.
+ *   status: int32 [1] on the device, written whole.  With m = the number of the cell's pixels found inside its box (clipped
+ *   to the frame), a rank outside 0 .. m - 1 writes 0 for that entry and sets status[0] != 0; the same holds for a frame's
+ *   background count.  With the status word set the outputs are NOT valid.  This is how a box that does not cover its cell
+ *   is caught.  No read or write ever leaves the arrays as sized here.
+ *   Exact radix select: a 256-bin histogram of the high byte (uint8: of the value), a prefix over the bins, and for uint16
+ *   a second walk for the low-byte histograms of the bins the ranks fell into.  Cells: one wave per cell slot, histograms
+ *   in LDS, no workspace.  Background: whole-frame passes, histograms merged in the workspace with integer atomics.
+ *   ws >= mseg_cell_order_stats_workspace_bytes (T * C * (256 + R * 256 + 4 R) words of 4 bytes, each of the three arrays
+ *   rounded up to 256 bytes; nothing per cell; 0 = bad arguments).  MSEG_EINVAL: bad sizes, R or C out of range, a dtype not
+ *   listed, H * W >= 2^31 - 512; MSEG_EWORKSPACE: ws_bytes too small; nothing is launched and nothing written on either.
+ *   n_labels == 0: only the background is measured (bbox, ranks and values may be NULL).                                  */
+size_t mseg_cell_order_stats_workspace_bytes(int T, int64_t n_labels, int C, int R);
+int mseg_cell_order_stats(const void* labels, int label_dtype, int T, int H, int W, const int64_t* label_off, int64_t n_labels,
+                          const void* img, int img_dtype, int C, int64_t frame_stride, int64_t chan_stride,
+                          int64_t row_stride, int64_t pix_stride, const int32_t* bbox, int R, const int64_t* ranks,
+                          const int64_t* bg_ranks, uint32_t* values, uint32_t* bg_values, int32_t* status, void* ws,
+                          size_t ws_bytes, void* stream);
 
 /* ---- training-set preparation (DataCropWorker src/utils/data_cropping.py:157-264,286,
  * DataImportWorker src/utils/data_import.py:125-194, DataExportWorker src/utils/data_export.py:100-101) -----------------

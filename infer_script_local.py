@@ -12,7 +12,8 @@ the GUI's Export button (inference/result_export.py) for the segmented channel o
 ``--scale S`` predicts every frame at S times its resolution and segments at its own (inference/resample.py);
 ``--drift [R]`` with ``--cells``: cells are linked under the stage drift found within +-R pixels (inference/cells.py);
 ``--hull`` with ``--cells``: perimeter, convex hull and Feret length / width / angle of every cell (inference/cells.py);
-``--midline`` with ``--cells``: the thinned midline of every cell: its length, for bent and filamentous cells (inference/cells.py).
+``--midline`` with ``--cells``: the thinned midline of every cell: its length, for bent and filamentous cells (inference/cells.py);
+``--percentiles [P ...]`` with ``--cells``: percentiles (default 50, the median) of every cell's pixel values and of the background.
 """
 import argparse
 from pathlib import Path
@@ -88,6 +89,14 @@ class Parser(argparse.ArgumentParser):
             self.error('--hull needs --cells (it adds columns to the cell table)')
         if ns.midline and not ns.cells:
             self.error('--midline needs --cells (it adds columns to the cell table)')
+        if ns.percentiles is not None:
+            if not ns.cells:
+                self.error('--percentiles needs --cells (it adds columns to the cell table)')
+            from microbeseg_amd.inference.cells import check_percentiles
+            try:
+                ns.percentiles = list(check_percentiles(ns.percentiles or [50]))     # the bare flag: the median
+            except ValueError as e:
+                self.error(f'--percentiles: {e}')
         if ns.scale != 1:
             if ns.tta > 1:
                 self.error('--scale and --tta > 1 cannot be combined')
@@ -172,6 +181,12 @@ def build_parser():
                              'filamentous cell, where feret_max is only its chord; NaN for branched or ring skeletons), '
                              'midline_width = area / midline_length and the two end points.  Whole pixels: no pruning, no '
                              'sub-pixel midline; for straight rods feret_max (--hull) is the better length')
+    parser.add_argument('--percentiles', nargs='*', default=None, type=int, metavar='P',
+                        help='[extension] with --cells: add p{P}_ch{c}, the P-th percentile of every cell\'s pixel values '
+                             'per measured channel, and bg_p{P}_ch{c}, the same over the frame\'s background (label 0): the '
+                             'robust counterparts of mean / max / bg_mean.  1 to 8 distinct whole numbers in 0 .. 100; the '
+                             'bare flag means 50, the median.  Exact order statistics from the device, linear '
+                             'interpolation as numpy\'s default; uint8 / uint16 images')
     return parser
 
 
@@ -215,6 +230,7 @@ def main():
     worker.drift = args.drift
     worker.hull = args.hull
     worker.midline = args.midline
+    worker.percentiles = tuple(args.percentiles) if args.percentiles else None
     worker.tta = args.tta
     worker.scale = args.scale
     if args.drift is not None:
@@ -223,6 +239,9 @@ def main():
         print('Cell table: with the outline measures (perimeter, convex hull, Feret length / width / angle)')
     if args.midline:
         print('Cell table: with the midline measures (thinned skeleton, midline length / width, end points)')
+    if args.percentiles:
+        print('Cell table: with the percentiles ' + ', '.join(str(q) for q in args.percentiles) +
+              ' of every cell and of the background per measured channel')
     if args.scale != 1:
         print(f'Inference at {args.scale} x the resolution of the frames')
     if args.tta > 1:

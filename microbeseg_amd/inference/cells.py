@@ -14,7 +14,11 @@ the measures of the cell's PIXEL OUTLINE people take from rod-shaped microbes: c
 smallest caliper (csrc/hull.hip: ``mseg_cell_hull``).  No sub-pixel contour is fitted.  ``midline=True`` adds the
 length along a BENT cell, where the largest caliper is only the chord: every cell is thinned alone to a one-pixel skeleton
 (Guo & Hall) and the skeleton is counted (csrc/midline.hip: ``mseg_cell_midline``).  Whole pixels: no
-pruning, no sub-pixel midline; for straight rods the caliper stays the better length.
+pruning, no sub-pixel midline; for straight rods the caliper stays the better length.  ``percentiles=(5, 50, 95)`` adds the
+ROBUST intensity columns: percentiles (50 = the median) of every cell's pixel values and of every frame's background per
+measured channel, where one hot pixel or a bright neighbour moves mean and max.  The device returns order statistics, the
+exact integers of given ranks (csrc/order_stats.hip: ``mseg_cell_order_stats``); the linear interpolation
+between two of them is numpy's, in fp64, here.  uint8 / uint16 images only, no other percentile method.
 """
 import ctypes as C
 import math
@@ -34,20 +38,25 @@ HULL_COLUMNS = ['perimeter', 'convex_area', 'solidity', 'feret_max', 'feret_min'
                 'feret_y1', 'feret_x1']
 MIDLINE_COLUMNS = ['skeleton_pixels', 'skeleton_length', 'skeleton_ends', 'skeleton_branches', 'midline_length',
                    'midline_width', 'midline_y0', 'midline_x0', 'midline_y1', 'midline_x1']
+PERCENTILE_COLUMNS = ['p{p}_ch{c}', 'bg_p{p}_ch{c}']     # all cell columns (channel by channel), then all background columns
+MAX_PERCENTILES = 8   # 2 ranks each: the 16 ranks mseg_cell_order_stats accepts
 MAX_DRIFT = 128       # largest search radius mseg_stack_drift accepts
 MIN_TABLE = 64        # smallest pair table mseg_cell_links accepts
 
 
-def columns(channels=(), link=True, drift=False, hull=False, midline=False):
+def columns(channels=(), link=True, drift=False, hull=False, midline=False, percentiles=()):
     """the table's columns, in order, for the measured ``channels``; ``drift``: with the drift columns (needs ``link``);
-    ``hull``: with the outline columns; ``midline``: with the midline columns, which come last"""
+    ``hull``: with the outline columns; ``midline``: with the midline columns; ``percentiles``: with p{P}_ch{c} for every
+    measured channel (per channel the percentiles in the order given), then bg_p{P}_ch{c} likewise; these come last"""
     if drift and not link:
         raise ValueError("the drift columns belong to the link columns: drift needs link")
     cols = list(SHAPE_COLUMNS)
     for c in channels:
         cols += [name.format(c=int(c)) for name in CHANNEL_COLUMNS]
     return cols + (list(LINK_COLUMNS) if link else []) + (list(DRIFT_COLUMNS) if drift else []) + \
-        (list(HULL_COLUMNS) if hull else []) + (list(MIDLINE_COLUMNS) if midline else [])
+        (list(HULL_COLUMNS) if hull else []) + (list(MIDLINE_COLUMNS) if midline else []) + \
+        [name.format(p=int(q), c=int(c)) for name in (PERCENTILE_COLUMNS if percentiles else ()) for c in channels
+         for q in percentiles]
 
 
 def _device(device=None):
@@ -256,6 +265,97 @@ def midline_raw(lab, pix, off, bbox, skeleton=False):
     return (ints, skel.cpu().numpy()) if skeleton else ints
 
 
+def check_percentiles(p):
+    """the rule of ``measure_cells(percentiles=...)``, ``InferWorker.percentiles`` and --percentiles: None or () = off;
+    else 1 .. 8 distinct whole numbers in 0 .. 100 -> a tuple of ints in the order given"""
+    if p is None:
+        return ()
+    try:
+        vals = list(p)
+    except TypeError:
+        raise ValueError(f"percentiles: None or a sequence of whole numbers in 0 .. 100 expected, got {p!r}") from None
+    out = []
+    for v in vals:
+        try:
+            ok = not isinstance(v, (bool, str, bytes)) and int(v) == v and 0 <= int(v) <= 100
+        except (TypeError, ValueError, OverflowError):
+            ok = False
+        if not ok:
+            raise ValueError(f"percentiles: whole numbers in 0 .. 100 expected, got {v!r}")
+        out.append(int(v))
+    if len(out) > MAX_PERCENTILES or len(set(out)) != len(out):
+        raise ValueError(f"percentiles: at most {MAX_PERCENTILES} distinct values expected, got {out}")
+    return tuple(out)
+
+
+def percentile_ranks(count, percentiles):
+    """The two order statistics numpy's linear rule reads for each percentile P of a sample of ``count`` values (an int or an
+    integer array): h = (count - 1) * (P / 100) in fp64, k = floor(h) -> ranks k and min(k + 1, count - 1), g = h - k.
+    -> (ranks int64 [2 * len(percentiles), *count.shape]: rows 2 i and 2 i + 1 belong to percentiles[i]; g fp64
+    [len(percentiles), *count.shape]).  A count of 0 gives rank 0 (which nobody reads) and g 0.  Pure numpy."""
+    n = np.asarray(count).astype(np.int64)
+    ranks = np.zeros((2 * len(percentiles),) + n.shape, np.int64)
+    g = np.zeros((len(percentiles),) + n.shape, np.float64)
+    top = np.maximum(n - 1, 0)
+    for i, q in enumerate(percentiles):
+        h = top.astype(np.float64) * (np.float64(q) / np.float64(100))
+        k = np.floor(h)
+        ranks[2 * i] = np.minimum(k.astype(np.int64), top)
+        ranks[2 * i + 1] = np.minimum(ranks[2 * i] + 1, top)
+        g[i] = h - k
+    return ranks, g
+
+
+def percentile_value(lo, hi, g):
+    """numpy's linear rule on the two order statistics: lo + (hi - lo) * g where g < 0.5, else hi - (hi - lo) * (1 - g); fp64"""
+    lo, hi, g = np.asarray(lo, np.float64), np.asarray(hi, np.float64), np.asarray(g, np.float64)
+    d = hi - lo
+    return np.where(g < 0.5, lo + d * g, hi - d * (1.0 - g))
+
+
+def order_stats_raw(lab, pix, off, image, channels, bbox, ranks, bg_ranks):
+    """``mseg_cell_order_stats`` for the whole stack, one call per channel group -> (values uint32 [R, C, n], bg_values uint32
+    [R, T, C]) on the host: per cell slot (frame) and channel the pixel value of rank ranks[j, s] (bg_ranks[j, t]) in ascending
+    order.  ``bbox``: int32 [n, 4], the boxes of ``measure_raw``; ranks int64 [R, n], bg_ranks int64 [R, T].  A rank beyond a
+    cell's pixels inside its box (or beyond a frame's background) makes the device set its status word, which raises here."""
+    lib = _lib.load()
+    dev = lab.device
+    T, H, W = (int(v) for v in lab.shape)
+    n = int(off[-1])
+    ranks = np.ascontiguousarray(ranks, np.int64)
+    bg_ranks = np.ascontiguousarray(bg_ranks, np.int64)
+    R = int(bg_ranks.shape[0])
+    if image is None or not len(channels):
+        raise ValueError("order statistics are taken of an image's channels: none given")
+    if bg_ranks.shape != (R, T) or ranks.shape != (R, n):
+        raise ValueError(f"ranks [{R}, {n}] and bg_ranks [{R}, {T}] expected, got {ranks.shape} and {bg_ranks.shape}")
+    off_d = torch.from_numpy(np.ascontiguousarray(off, np.int64)).to(dev)
+    bbox_d = torch.from_numpy(np.ascontiguousarray(bbox, np.int32).reshape(n, 4)).to(dev) if n else None
+    ranks_d = torch.from_numpy(ranks).to(dev) if n else None
+    bg_ranks_d = torch.from_numpy(bg_ranks).to(dev)
+    _, base, ipix, _, (fs, cs0, rs, ps) = image
+    vals, bgs = [], []
+    for first, step, Cg in _channel_groups(list(channels)):
+        nbytes = lib.mseg_cell_order_stats_workspace_bytes(T, n, Cg, R)
+        if nbytes == 0:
+            raise ValueError(f"mseg_cell_order_stats: no workspace for T = {T}, {Cg} channels, {R} ranks")
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        out = torch.zeros(R * Cg * n + R * T * Cg + 1, dtype=torch.int32, device=dev)      # values, bg_values, status: one download
+        v_ptr, b_ptr = out.data_ptr(), out.data_ptr() + 4 * R * Cg * n
+        _lib.check(lib.mseg_cell_order_stats(lab.data_ptr(), pix, T, H, W, off_d.data_ptr(), n,
+                                             base + first * cs0 * (1 if ipix == _lib.PIX_U8 else 2), ipix, Cg, fs, step * cs0,
+                                             rs, ps, bbox_d.data_ptr() if n else None, R, ranks_d.data_ptr() if n else None,
+                                             bg_ranks_d.data_ptr(), v_ptr if n else None, b_ptr, b_ptr + 4 * R * T * Cg,
+                                             ws.data_ptr(), ws.numel(), _stream(dev)), "cell_order_stats")
+        host = out.cpu().numpy().view(np.uint32)
+        if host[-1] != 0:
+            raise RuntimeError("mseg_cell_order_stats: a rank lies beyond the pixels of a cell inside the bounding box given "
+                               "for it (or beyond a frame's background)")
+        vals.append(host[:R * Cg * n].reshape(R, Cg, n))
+        bgs.append(host[R * Cg * n:-1].reshape(R, T, Cg))
+    return np.concatenate(vals, axis=1), np.concatenate(bgs, axis=2)
+
+
 def _pow2(v):
     return 1 << max(int(v) - 1, 0).bit_length()
 
@@ -432,7 +532,8 @@ def _midline(area, m):
     return [skel_n, chain, n_end, n_branch, length, area / length, y0, x0, y1, x1]
 
 
-def table_from_sums(off, H, W, raw, channels=(), links=None, min_overlap=1, shift=None, hull=None, midline=None):
+def table_from_sums(off, H, W, raw, channels=(), links=None, min_overlap=1, shift=None, hull=None, midline=None,
+                    order_stats=None):
     """the DataFrame from the integer sums of ``measure_raw`` (and ``links`` = (pred, overlap) or None); host arithmetic in
     Python integers and fp64.  ``shift``: int [T, 2], the (dy, dx) of every frame against its predecessor the links were
     taken under (row 0 ignored), or None: with it the drift columns follow the link columns.  ``hull``: int [10, n], the
@@ -442,10 +543,24 @@ def table_from_sums(off, H, W, raw, channels=(), links=None, min_overlap=1, shif
     [12, n], the integers of ``midline_raw``, or None: with it the table ends with the midline columns: skeleton_pixels =
     skel_n, skeleton_length = n_orth + sqrt(2) n_diag, skeleton_ends, skeleton_branches, midline_length = skeleton_length +
     sqrt(e0_d2) + sqrt(e1_d2) - 1 where the skeleton is one open chain (n_end == 2 and n_branch == 0) or one pixel, NaN
-    otherwise, midline_width = area / midline_length, and the two end points (0 where there are none)"""
+    otherwise, midline_width = area / midline_length, and the two end points (0 where there are none).  ``order_stats``:
+    (percentiles, values uint32 [2 P, C, n], bg_values uint32 [2 P, T, C]): the integers of ``order_stats_raw`` for the ranks
+    of ``percentile_ranks`` (cell counts: raw["shape"][0], background counts: raw["bg_sums"][0]), or None: with it the table
+    ends with p{P}_ch{c} = ``percentile_value`` of the two order statistics, and bg_p{P}_ch{c} (NaN without background)"""
     off = np.asarray(off, np.int64)
     area = raw["shape"][0]
-    rows = {c: [] for c in columns(channels, links is not None, shift is not None, hull is not None, midline is not None)}
+    pct = check_percentiles(order_stats[0]) if order_stats is not None else ()
+    if pct and not len(channels):
+        raise ValueError("percentiles are taken of an image's channels: none is measured")
+    rows = {c: [] for c in columns(channels, links is not None, shift is not None, hull is not None, midline is not None, pct)}
+    if pct:
+        vals = np.asarray(order_stats[1]).reshape(2 * len(pct), len(channels), len(area))
+        bgv = np.asarray(order_stats[2]).reshape(2 * len(pct), len(off) - 1, len(channels))
+        bg_n = np.asarray(raw["bg_sums"][0]).astype(np.int64)                                # [T, C]
+        g = percentile_ranks(np.asarray(area).astype(np.int64), pct)[1]                       # [P, n]
+        cell_p = percentile_value(vals[0::2], vals[1::2], g[:, None, :])                      # [P, C, n]
+        bg_p = np.where(bg_n[None] > 0, percentile_value(bgv[0::2], bgv[1::2], percentile_ranks(bg_n, pct)[1]), np.nan)
+        cell_p, bg_p = cell_p.tolist(), bg_p.tolist()                                         # Python floats, as every column
     if hull is not None:
         hl = [[int(v) for v in plane] for plane in np.asarray(hull).reshape(10, len(area))]
     if midline is not None:
@@ -480,6 +595,9 @@ def table_from_sums(off, H, W, raw, channels=(), links=None, min_overlap=1, shif
                 vals += _outline(n, [plane[s] for plane in hl])
             if midline is not None:
                 vals += _midline(n, [plane[s] for plane in ml])
+            if pct:
+                vals += [cell_p[i][ci][s] for ci in range(len(channels)) for i in range(len(pct))]
+                vals += [bg_p[i][t][ci] for ci in range(len(channels)) for i in range(len(pct))]
             for c, v in zip(rows, vals):
                 rows[c].append(v)
     df = pd.DataFrame(rows, columns=list(rows))
@@ -491,7 +609,7 @@ def table_from_sums(off, H, W, raw, channels=(), links=None, min_overlap=1, shif
 
 
 def measure_cells(mask, img=None, channels=None, link=True, min_overlap=1, device=None, drift=None, hull=False,
-                  midline=False):
+                  midline=False, percentiles=None):
     """ One row per cell of a segmented stack, ordered by (frame, label).
 
     :param mask: label stack [T, H, W] (or one frame [H, W]): host array or device tensor (int16 holding uint16 bits, or
@@ -518,9 +636,18 @@ def measure_cells(mask, img=None, channels=None, link=True, min_overlap=1, devic
         (skeleton_ends / skeleton_branches say which; boundary noise can branch a skeleton, nothing is pruned).  Chain
         lengths depend on the direction (about -11 % at 45 degrees): for straight rods feret_max is the better length, for
         round cells the midline means nothing.  Needs neither ``link`` nor ``hull``.
-    :return: pandas.DataFrame with the columns of ``columns(channels, link, drift is not None, hull, midline)``.
+    :param percentiles: None or () (default): off.  1 .. 8 distinct whole numbers in 0 .. 100, e.g. (5, 50, 95): the table
+        ends with p{P}_ch{c}, the P-th percentile of the cell's pixel values in every measured channel (p50 is the median),
+        and bg_p{P}_ch{c}, the same over the frame's label-0 pixels (NaN for a frame without background): what one hot
+        pixel, a bright neighbour or debris in the background does not move.  Linear interpolation between the two nearest
+        order statistics, as ``np.percentile`` does by default; the order statistics are exact integers from the device.
+        Needs ``img`` and at least one measured channel.
+    :return: pandas.DataFrame with the columns of ``columns(channels, link, drift is not None, hull, midline, percentiles)``.
     """
     drift = check_drift(drift)
+    percentiles = check_percentiles(percentiles)
+    if percentiles and img is None:
+        raise ValueError("percentiles are taken of an image's channels: no image given")
     if drift is not None and not link:
         raise ValueError("drift changes how cells are linked: it needs link=True")
     dev = _device(device)
@@ -539,12 +666,19 @@ def measure_cells(mask, img=None, channels=None, link=True, min_overlap=1, devic
                 raise ValueError(f"channels {channels} requested, the image has {image[3]}")
         else:
             channels = []
+        if percentiles and not channels:
+            raise ValueError("percentiles are taken of an image's channels: none is measured")
         raw = measure_raw(lab, pix, off, image, channels)
         shift = pick_drift(drift_raw(lab, pix, off, drift)) if drift is not None else None
         links = link_raw(lab, pix, off, shift=shift) if link else None
         outline = hull_raw(lab, pix, off, raw["bbox"]) if hull else None
         skel = midline_raw(lab, pix, off, raw["bbox"]) if midline else None
-    return table_from_sums(off, H, W, raw, channels, links, min_overlap, shift, outline, skel)
+        stats = None
+        if percentiles:
+            ranks = percentile_ranks(raw["shape"][0].astype(np.int64), percentiles)[0]
+            bg_ranks = percentile_ranks(raw["bg_sums"][0, :, 0].astype(np.int64), percentiles)[0]
+            stats = (percentiles,) + order_stats_raw(lab, pix, off, image, channels, raw["bbox"], ranks, bg_ranks)
+    return table_from_sums(off, H, W, raw, channels, links, min_overlap, shift, outline, skel, stats)
 
 
 def write_cells(df, csv_path):
