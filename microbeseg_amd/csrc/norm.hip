@@ -139,6 +139,11 @@ __device__ __forceinline__ bool norm_arrive(unsigned* ctr, unsigned expected, in
   return *s_flag != 0;
 }
 
+// A statistic taken over ONE value (one pixel per channel under Batch / InstanceNorm): y = beta whatever a is, so dz, and the
+// sum of gy xhat, are exactly 0.  The tables k1 gy + k2 a + k3 cancel only to rounding there — rstd = 1 / sqrt(eps) leaves
+// |dz| of the order of 2^-24 rstd |gy| = 2e-5 |gy| — so they are written as zeros: 0 for such a statistic, else 1.
+__device__ __forceinline__ double norm_bwd_live(double cnt) { return cnt > 1.0 ? 1.0 : 0.0; }
+
 #define NORM_TAIL_NONE 0
 #define NORM_TAIL_BN_FWD 1     // statistics -> scale / shift / mean / rstd / running statistics
 #define NORM_TAIL_PS_FWD 2     // the same per sample (GroupNorm, InstanceNorm)
@@ -392,7 +397,7 @@ __global__ __launch_bounds__(256) void norm_pass_kernel(const void* __restrict__
         const double cnt = (double)cg * g.HW;
         const double mean = sm / cnt;
         double var = q / cnt - mean * mean;
-        if (var < 0.0) var = 0.0;
+        if (var < 0.0 || cnt <= 1.0) var = 0.0;         // (one value: E[a^2] - mean^2 holds only the rounding of a^2)
         const double rstd = 1.0 / sqrt(var + (double)t.eps);
         red[tid] = mean; red[128 + tid] = rstd;
         t.mean_out[n * groups + grp] = (float)mean;
@@ -436,7 +441,7 @@ __global__ __launch_bounds__(256) void norm_pass_kernel(const void* __restrict__
       } else if (t.kind == NORM_TAIL_BN_FWD) {
         const double mean = a0 / cnt;
         double var = b0 / cnt - mean * mean;
-        if (var < 0.0) var = 0.0;
+        if (var < 0.0 || cnt <= 1.0) var = 0.0;         // (one value: E[a^2] - mean^2 holds only the rounding of a^2)
         const double rstd = 1.0 / sqrt(var + (double)t.eps);
         const double ga = t.gamma ? (double)t.gamma[c2] : 1.0, be = t.beta ? (double)t.beta[c2] : 0.0;
         t.scale[c2] = (float)(ga * rstd);
@@ -450,11 +455,12 @@ __global__ __launch_bounds__(256) void norm_pass_kernel(const void* __restrict__
         }
       } else {                                         // NORM_TAIL_BN_BWD: a0 = sum gy, b0 = sum gy a
         const double mu = t.mean[c2], r = t.rstd[c2], ga = t.gamma ? (double)t.gamma[c2] : 1.0;
-        const double sx = r * (b0 - mu * a0);          // sum gy * xhat
+        const double live = norm_bwd_live(cnt);
+        const double sx = live * r * (b0 - mu * a0);   // sum gy * xhat
         const double m1 = ga * a0 / cnt, m2 = ga * sx / cnt;
-        t.k1[c2] = (float)(ga * r);
+        t.k1[c2] = (float)(live * ga * r);
         t.k2[c2] = (float)(-r * r * m2);
-        t.k3[c2] = (float)(-r * m1 + r * r * m2 * mu);
+        t.k3[c2] = (float)(live * (-r * m1 + r * r * m2 * mu));
         if (t.dgamma) t.dgamma[c2] = (float)sx;
         if (t.dbeta) t.dbeta[c2] = (float)a0;
       }
@@ -519,7 +525,7 @@ __device__ __forceinline__ void norm_fwd_finalize_body(const double* __restrict_
       const double cnt = count > 0.0 ? count : (double)g.N * g.HW;
       const double mean = s / cnt;
       double var = q / cnt - mean * mean;
-      if (var < 0.0) var = 0.0;
+      if (var < 0.0 || cnt <= 1.0) var = 0.0;         // (one value: E[a^2] - mean^2 holds only the rounding of a^2)
       const double rstd = 1.0 / sqrt(var + (double)eps);
       const double ga = gamma ? (double)gamma[c] : 1.0, be = beta ? (double)beta[c] : 0.0;
       scale[c] = (float)(ga * rstd);
@@ -548,7 +554,7 @@ __device__ __forceinline__ void norm_fwd_finalize_body(const double* __restrict_
     const double cnt = (double)cg * g.HW;
     const double mean = s / cnt;
     double var = q / cnt - mean * mean;
-    if (var < 0.0) var = 0.0;
+    if (var < 0.0 || cnt <= 1.0) var = 0.0;         // (one value: E[a^2] - mean^2 holds only the rounding of a^2)
     const double rstd = 1.0 / sqrt(var + (double)eps);
     const double ga = (norm == MSEG_NORM_GN && gamma) ? (double)gamma[c] : 1.0;
     const double be = (norm == MSEG_NORM_GN && beta) ? (double)beta[c] : 0.0;
@@ -587,11 +593,12 @@ __device__ __forceinline__ void norm_bwd_finalize_body(const double* __restrict_
       for (int n = 0; n < g.N; ++n) { s1 += S1[(size_t)n * g.C + c]; s2 += S2[(size_t)n * g.C + c]; }
       const double cnt = (double)g.N * g.HW;
       const double mu = mean[c], r = rstd[c], ga = gamma ? (double)gamma[c] : 1.0;
-      const double sx = r * (s2 - mu * s1);  // sum gy * xhat
+      const double live = norm_bwd_live(cnt);
+      const double sx = live * r * (s2 - mu * s1);  // sum gy * xhat
       const double m1 = ga * s1 / cnt, m2 = ga * sx / cnt;
-      k1[c] = (float)(ga * r);
+      k1[c] = (float)(live * ga * r);
       k2[c] = (float)(-r * r * m2);
-      k3[c] = (float)(-r * m1 + r * r * m2 * mu);
+      k3[c] = (float)(live * (-r * m1 + r * r * m2 * mu));
       if (dgamma) dgamma[c] = (float)sx;
       if (dbeta) dbeta[c] = (float)s1;
     }
@@ -613,11 +620,13 @@ __device__ __forceinline__ void norm_bwd_finalize_body(const double* __restrict_
       m2 += ga * r * (s2 - mu * s1);
     }
     const double cnt = (double)cg * g.HW;
+    const double live = norm_bwd_live(cnt);
     m1 /= cnt; m2 /= cnt;
+    m2 *= live;
     const double gac = (norm == MSEG_NORM_GN && gamma) ? (double)gamma[c] : 1.0;
-    k1[i] = (float)(gac * r);
+    k1[i] = (float)(live * gac * r);
     k2[i] = (float)(-r * r * m2);
-    k3[i] = (float)(-r * m1 + r * r * m2 * mu);
+    k3[i] = (float)(live * (-r * m1 + r * r * m2 * mu));
   }
   if (norm == MSEG_NORM_GN && dgamma) {
     // dgamma_c = sum_n rstd*(S2 - mean*S1), dbeta_c = sum_n S1   (one thread per channel, fixed order)
@@ -738,7 +747,7 @@ __global__ __launch_bounds__(1024) void norm_bn_finish_kernel(const double* __re
     const double cnt = (double)g.N * g.HW;
     const double mean = a0 / cnt;
     double var = b0 / cnt - mean * mean;
-    if (var < 0.0) var = 0.0;
+    if (var < 0.0 || cnt <= 1.0) var = 0.0;         // (one value: E[a^2] - mean^2 holds only the rounding of a^2)
     const double rstd = 1.0 / sqrt(var + (double)t.eps);
     const double ga = t.gamma ? (double)t.gamma[c] : 1.0, be = t.beta ? (double)t.beta[c] : 0.0;
     t.scale[c] = (float)(ga * rstd);
@@ -753,11 +762,12 @@ __global__ __launch_bounds__(1024) void norm_bn_finish_kernel(const double* __re
   } else if (t.kind == NORM_TAIL_BN_BWD) {             // a0 = sum gy, b0 = sum gy a
     const double cnt = (double)g.N * g.HW;
     const double mu = t.mean[c], r = t.rstd[c], ga = t.gamma ? (double)t.gamma[c] : 1.0;
-    const double sx = r * (b0 - mu * a0);              // sum gy * xhat
+    const double live = norm_bwd_live(cnt);
+    const double sx = live * r * (b0 - mu * a0);       // sum gy * xhat
     const double m1 = ga * a0 / cnt, m2 = ga * sx / cnt;
-    t.k1[c] = (float)(ga * r);
+    t.k1[c] = (float)(live * ga * r);
     t.k2[c] = (float)(-r * r * m2);
-    t.k3[c] = (float)(-r * m1 + r * r * m2 * mu);
+    t.k3[c] = (float)(live * (-r * m1 + r * r * m2 * mu));
     if (t.dgamma) t.dgamma[c] = (float)sx;
     if (t.dbeta) t.dbeta[c] = (float)a0;
   } else {
