@@ -1,6 +1,7 @@
 """Host: the plain references of tests/conv_ref.py against torch.nn.functional in fp64 (values, and gradients through
 autograd) on a few odd shapes — N > 1, H != W, stride 2 on odd and even sizes, channel counts off every tile size — so that
-the GPU tests of the convolution kernels can use them as the yardstick."""
+the GPU tests of the convolution kernels can use them as the yardstick; and the bf16 rounding, the bf16 operand with its
+ambiguity field and the widening condition of the bf16 table (tests/test_gpu_conv_bf16.py)."""
 import numpy as np
 import pytest
 import torch
@@ -140,3 +141,80 @@ def test_exact_mode_is_integer_arithmetic():
         CR.as_exact(np.array([0.5]))
     with pytest.raises(AssertionError):
         CR.assert_exact(np.array([2 ** 24], dtype=np.int64))
+
+
+# ---- bf16: rounding, the kernels' operand, and the widening condition of the bf16 table -------------------------------------------
+def _f32(bits):
+    return np.array(bits, dtype=np.uint32).view(np.float32)
+
+
+def _torch_bf16(a32):
+    return torch.from_numpy(np.ascontiguousarray(a32)).to(torch.bfloat16).to(torch.float64).numpy()
+
+
+def test_round_bf16_equals_torch_on_the_hard_values():
+    """ties to even both ways, -0.0, bf16 subnormals, the largest finite value, one fp32 ulp either side of every tie, and a
+    random sweep of bit patterns; bit for bit (the sign of zero included)"""
+    ties = [0x3F808000, 0x3F818000, 0xBF808000, 0xBF818000, 0x40FF8000, 0x00008000, 0x00018000, 0x80008000, 0x7F7E8000,
+            0x007F8000, 0x00808000]                                   # ...8000: exactly half way; even / odd kept mantissa
+    bits = []
+    for t in ties:
+        bits += [t - 1, t, t + 1]
+    bits += [0x00000000, 0x80000000, 0x00000001, 0x00010000, 0x00004000, 0x007F0000, 0x7F7F0000, 0xFF7F0000, 0x7F7F7FFF,
+             0x7F7F8000, 0x7F7FFFFF, 0x7F800000, 0xFF800000]          # zeros, subnormals, largest finite, overflow, infinities
+    g = _rng(5)
+    bits += [int(v) for v in g.integers(0, 2 ** 32, size=20000) if (int(v) >> 23) & 0xFF != 0xFF]
+    a = _f32(bits)
+    got, want = CR.round_bf16(a), _torch_bf16(a)
+    assert np.array_equal(got, want) and np.array_equal(np.signbit(got), np.signbit(want))
+    # from fp64 there is no detour through fp32: a value just above a tie that fp32 would round ONTO the tie goes up
+    x = 1.0 + 2.0 ** -8 + 2.0 ** -40
+    assert CR.round_bf16(np.array([x]))[0] == 1.0 + 2.0 ** -7 and _torch_bf16(np.array([x], dtype=np.float32))[0] == 1.0
+    assert CR.round_bf16(np.array([1.0 + 2.0 ** -8]))[0] == 1.0 and CR.round_bf16(np.array([1.0 + 3 * 2.0 ** -8]))[0] == 1.0 + 2.0 ** -6
+    assert np.array_equal(CR.bf16_ulp(np.array([1.0, 1.99, 2.0, 0.0, 3e-39])), [2.0 ** -7, 2.0 ** -7, 2.0 ** -6, 2.0 ** -133, 2.0 ** -133])
+
+
+@pytest.mark.parametrize("act", R.ACTS)
+def test_operand_bf16(act):
+    """the operand is torch's bf16 rounding of torch's fp32 transform wherever it is not flagged ambiguous; a flagged one
+    is at most one bf16 ulp away and A is exactly that ulp; a plain source is rounded directly and never flagged"""
+    g = _rng(9)
+    z = (g.normal(size=(2, 9, 11, 16)) * 2).astype(np.float32)
+    z[0, 0, 0, :4] = [-0.0, 0.0, -1.0, 1.0 + 2.0 ** -8]
+    sc, sh = (1 + 0.3 * g.normal(size=16)).astype(np.float32), g.normal(size=(16,)).astype(np.float32)
+    zt = torch.from_numpy(z)
+    t32 = R.activation(zt, act, dtype=torch.float32) * torch.from_numpy(sc) + torch.from_numpy(sh)
+    want = t32.to(torch.bfloat16).to(torch.float64).numpy()
+    op, A = CR.operand_bf16(z, act, sc, sh)
+    clear = A == 0
+    assert clear.mean() > 0.98
+    assert np.array_equal(op[clear], want[clear])
+    assert (np.abs(op - want)[~clear] <= A[~clear]).all() and np.array_equal(A[~clear], CR.bf16_ulp(op[~clear]))
+    if act == "none":
+        op0, A0 = CR.operand_bf16(z)
+        assert not A0.any() and np.array_equal(op0, _torch_bf16(z))
+    if act == "relu":                                                   # exact small integers, negative scale, -0.0: no rounding
+        zi = g.integers(-3, 4, size=(1, 4, 4, 8)).astype(np.float32)
+        zi[0, 0, 0, 0] = -0.0
+        si, hi = np.array([-2, -1, 1, 2, 3, -2, 3, 1], np.float32), np.array([-2, -1, 1, 2, 2, 1, -1, -2], np.float32)
+        opi, Ai = CR.operand_bf16(zi, "relu", si, hi)
+        assert np.array_equal(opi, np.maximum(zi, 0) * si + hi) and np.abs(opi).max() <= 11
+        assert not Ai.any()
+
+
+def test_bf16_table_widening_condition():
+    """every row of the bf16 table, every float variant and seed the GPU test uses: the widening of every output element
+    stays within a quarter of the element's mean term, S / (4 K).  A row that breaks this gets another seed."""
+    import conv_table as T
+    import test_gpu_conv_bf16 as B
+    worst = 0.0
+    for r in B.ROWS:
+        K = T.geom(r)["dot"]
+        for i, (acts, pact) in enumerate(T.float_variants(r)):
+            if not B.transformed(r, acts, pact):
+                continue                                                # plain operands are rounded directly: nothing ambiguous
+            d = T.make_data(r, "float", acts, pact, B._seed(r, 1 + i), want_ref=False)
+            share = float((d["wid"] / (np.maximum(d["S"], T.TINY) / K)).max())
+            worst = max(worst, share)
+            assert share <= 0.25, (r.id, acts, pact, share)
+    assert worst > 0.0                                                  # the condition is not vacuous: some operand is ambiguous
