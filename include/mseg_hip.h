@@ -686,6 +686,41 @@ int mseg_cell_order_stats(const void* labels, int label_dtype, int T, int H, int
                           const int64_t* bg_ranks, uint32_t* values, uint32_t* bg_values, int32_t* status, void* ws,
                           size_t ws_bytes, void* stream);
 
+/* ---- per-cell neighbourhood (csrc/neighbors.hip) — an extension ------------------------------------------
+ * labels, dtype and label_off as for mseg_cell_links: cell l of frame t has slot label_off[t] + l - 1; ids beyond the frame's
+ * table and negative ids are not a cell, neither as a pixel nor as a neighbour: they count as background.  H * W < 2^31 - 512.
+ * radius = R, 1 <= R <= 32.  table_cap: entries of the pair table of every frame, a power of two, 64 <= table_cap <= 2^31.
+ * All within one frame, for two different cells a < b:
+ *   edges(a, b) = the unit pixel edges with a pixel of a on one side and a pixel of b on the other (4-neighbour pairs)
+ *   d2(a, b)    = the smallest dy^2 + dx^2 over pixels p of a and q of b, (dy, dx) the difference of their coordinates
+ *   the pair EXISTS when d2(a, b) <= R^2 (an edge-sharing pair has d2 = 1; one touching at a corner only has d2 = 2)
+ * mseg_cell_neighbors: outputs, all integers, written whole by the call, identical values from run to run:
+ *   out: int64 [9][n_labels], nine zeros for an absent id:
+ *     0 contact_edges        the sum of edges(a, .) over all other cells
+ *     1 border_edges         unit edges between a pixel of the cell and the outside of the frame
+ *     2 free_edges           unit edges between a pixel of the cell and a pixel that is not of a cell
+ *     3 n_touch              cells b with edges(a, b) > 0
+ *     4 n_near               existing pairs the cell is in (n_touch <= n_near)
+ *     5 nn_label             the other cell of the existing pair with the smallest d2, ties to the smallest label; 0: none
+ *     6 nn_d2                that pair's d2; 0: none
+ *     7 contact_label        the cell sharing the most edges, ties to the smallest label; 0: none shares an edge
+ *     8 contact_label_edges  that pair's edges; 0: none
+ *     planes 0 + 1 + 2 = plane 0 (perimeter) of mseg_cell_hull; the edges of holes count.
+ *   pairs: int32 [pair_cap][5] = frame, a, b, edges, d2: one row per existing pair, a < b, in no particular order.
+ *   n_pairs: int64 [1] on the device: the existing pairs of the whole stack, always the full count; beyond pair_cap rows
+ *     nothing is written (which pairs are then written is unspecified).  pairs == NULL with pair_cap == 0 is legal.
+ *   status: int32 [T] on the device; status[t] != 0: the pair table of frame t was full, frame t's slots of out and its pair
+ *     rows are then NOT valid, n_pairs is a lower bound, and the frame has to be redone with a larger table.  A frame of K
+ *     cells has at most K (K - 1) / 2 pairs.
+ *   ws >= mseg_cell_neighbors_workspace_bytes (16 bytes per table entry and frame + 16 per cell, each of the five arrays
+ *   rounded up to 256 bytes; 0 = bad arguments).  MSEG_EINVAL: bad sizes, R outside 1 .. 32, a dtype not listed, a table_cap
+ *   that is not a power of two in range, H * W >= 2^31 - 512; MSEG_EWORKSPACE: ws_bytes too small; nothing is launched and no
+ *   output is touched on either.  n_labels == 0: status and n_pairs = 0 alone.                                           */
+size_t mseg_cell_neighbors_workspace_bytes(int T, int64_t n_labels, int64_t table_cap);
+int mseg_cell_neighbors(const void* labels, int dtype, int T, int H, int W, const int64_t* label_off, int64_t n_labels,
+                        int radius, int64_t table_cap, int64_t* out, int32_t* pairs, int64_t pair_cap, int64_t* n_pairs,
+                        int32_t* status, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- training-set preparation (DataCropWorker src/utils/data_cropping.py:157-264,286,
  * DataImportWorker src/utils/data_import.py:125-194, DataExportWorker src/utils/data_export.py:100-101) -----------------
  * mseg_frame_stats: out[4] (device) = {min, max, sum v, sum v^2} of one uint8 / uint16 frame, exact, one pass (replaces

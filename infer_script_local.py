@@ -13,7 +13,8 @@ the GUI's Export button (inference/result_export.py) for the segmented channel o
 ``--drift [R]`` with ``--cells``: cells are linked under the stage drift found within +-R pixels (inference/cells.py);
 ``--hull`` with ``--cells``: perimeter, convex hull and Feret length / width / angle of every cell (inference/cells.py);
 ``--midline`` with ``--cells``: the thinned midline of every cell: its length, for bent and filamentous cells (inference/cells.py);
-``--percentiles [P ...]`` with ``--cells``: percentiles (default 50, the median) of every cell's pixel values and of the background.
+``--percentiles [P ...]`` with ``--cells``: percentiles (default 50, the median) of every cell's pixel values and of the background;
+``--neighbors [R]`` with ``--cells``: every cell's contacts and nearest neighbour within R pixels, and ``..._contacts.csv``, the pairs.
 """
 import argparse
 from pathlib import Path
@@ -97,6 +98,14 @@ class Parser(argparse.ArgumentParser):
                 ns.percentiles = list(check_percentiles(ns.percentiles or [50]))     # the bare flag: the median
             except ValueError as e:
                 self.error(f'--percentiles: {e}')
+        if ns.neighbors is not None:
+            if not ns.cells:
+                self.error('--neighbors needs --cells (it adds columns to the cell table)')
+            from microbeseg_amd.inference.cells import check_neighbors
+            try:
+                ns.neighbors = check_neighbors(ns.neighbors)
+            except ValueError as e:
+                self.error(f'--neighbors: {e}')
         if ns.scale != 1:
             if ns.tta > 1:
                 self.error('--scale and --tta > 1 cannot be combined')
@@ -187,6 +196,15 @@ def build_parser():
                              'robust counterparts of mean / max / bg_mean.  1 to 8 distinct whole numbers in 0 .. 100; the '
                              'bare flag means 50, the median.  Exact order statistics from the device, linear '
                              'interpolation as numpy\'s default; uint8 / uint16 images')
+    parser.add_argument('--neighbors', nargs='?', const=8, default=None, type=int, metavar='R',
+                        help='[extension] with --cells: add every cell\'s neighbourhood within its frame: contact_length / '
+                             'border_length / contact_fraction (pixel edges shared with other cells, with the frame\'s border, '
+                             'and the share of the former in the perimeter), n_touching, n_neighbors (cells within R pixels, '
+                             'default R = 8, 1 <= R <= 32), nn_label / nn_distance / nn_gap (the nearest of them) and '
+                             'contact_label / contact_max (the cell sharing the most edges); also write <mask file '
+                             'stem>_contacts.csv, one row per pair of cells within R: frame, label_a, label_b, contact, '
+                             'distance.  Whole pixels, centre-to-centre distances: no sub-pixel contour, nothing beyond R, no '
+                             'Voronoi or Delaunay neighbourhood')
     return parser
 
 
@@ -231,6 +249,7 @@ def main():
     worker.hull = args.hull
     worker.midline = args.midline
     worker.percentiles = tuple(args.percentiles) if args.percentiles else None
+    worker.neighbors = args.neighbors
     worker.tta = args.tta
     worker.scale = args.scale
     if args.drift is not None:
@@ -242,6 +261,9 @@ def main():
     if args.percentiles:
         print('Cell table: with the percentiles ' + ', '.join(str(q) for q in args.percentiles) +
               ' of every cell and of the background per measured channel')
+    if args.neighbors is not None:
+        print(f'Cell table: with the neighbourhood of every cell within {args.neighbors} px (contacts, nearest neighbour); '
+              'the pairs go to ..._contacts.csv')
     if args.scale != 1:
         print(f'Inference at {args.scale} x the resolution of the frames')
     if args.tta > 1:
@@ -282,6 +304,8 @@ def main():
                 print(f'Skip intensity columns of {img_id.stem} (they need uint8 / uint16 images, got {view.dtype})')
                 view, channels = None, []
             write_cells(worker.cell_table(results, view, channels), out_file.with_name(out_file.stem + '_cells.csv'))
+            if args.neighbors is not None:
+                write_cells(worker.contact_table(results), out_file.with_name(out_file.stem + '_contacts.csv'))
     print('--- Finished ---')
 
 

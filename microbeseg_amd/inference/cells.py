@@ -18,7 +18,12 @@ pruning, no sub-pixel midline; for straight rods the caliper stays the better le
 ROBUST intensity columns: percentiles (50 = the median) of every cell's pixel values and of every frame's background per
 measured channel, where one hot pixel or a bright neighbour moves mean and max.  The device returns order statistics, the
 exact integers of given ranks (csrc/order_stats.hip: ``mseg_cell_order_stats``); the linear interpolation
-between two of them is numpy's, in fp64, here.  uint8 / uint16 images only, no other percentile method.
+between two of them is numpy's, in fp64, here.  uint8 / uint16 images only, no other percentile method.  ``neighbors=R`` adds
+every cell's NEIGHBOURHOOD within its frame: how many unit pixel edges it shares with other cells, with the frame's border
+and with background, how many cells touch it, how many lie within R pixels, the nearest of them and the one it shares the
+most edges with (csrc/neighbors.hip: ``mseg_cell_neighbors``); ``cell_contacts`` returns the contact graph
+itself, one row per pair of cells within R.  Whole pixels only: distances are centre-to-centre distances of pixels, no
+sub-pixel contour is fitted, nothing beyond R is seen, and this is no Voronoi or Delaunay neighbourhood.
 """
 import ctypes as C
 import math
@@ -41,13 +46,18 @@ MIDLINE_COLUMNS = ['skeleton_pixels', 'skeleton_length', 'skeleton_ends', 'skele
 PERCENTILE_COLUMNS = ['p{p}_ch{c}', 'bg_p{p}_ch{c}']     # all cell columns (channel by channel), then all background columns
 MAX_PERCENTILES = 8   # 2 ranks each: the 16 ranks mseg_cell_order_stats accepts
 MAX_DRIFT = 128       # largest search radius mseg_stack_drift accepts
-MIN_TABLE = 64        # smallest pair table mseg_cell_links accepts
+NEIGHBOR_COLUMNS = ['contact_length', 'border_length', 'contact_fraction', 'n_touching', 'n_neighbors', 'nn_label',
+                    'nn_distance', 'nn_gap', 'contact_label', 'contact_max']
+CONTACT_COLUMNS = ['frame', 'label_a', 'label_b', 'contact', 'distance']
+MIN_TABLE = 64        # smallest pair table mseg_cell_links and mseg_cell_neighbors accept
+MAX_NEIGHBOR_RADIUS = 32   # largest radius mseg_cell_neighbors accepts
 
 
-def columns(channels=(), link=True, drift=False, hull=False, midline=False, percentiles=()):
+def columns(channels=(), link=True, drift=False, hull=False, midline=False, percentiles=(), neighbors=False):
     """the table's columns, in order, for the measured ``channels``; ``drift``: with the drift columns (needs ``link``);
     ``hull``: with the outline columns; ``midline``: with the midline columns; ``percentiles``: with p{P}_ch{c} for every
-    measured channel (per channel the percentiles in the order given), then bg_p{P}_ch{c} likewise; these come last"""
+    measured channel (per channel the percentiles in the order given), then bg_p{P}_ch{c} likewise; ``neighbors``: with the
+    neighbourhood columns; these come last"""
     if drift and not link:
         raise ValueError("the drift columns belong to the link columns: drift needs link")
     cols = list(SHAPE_COLUMNS)
@@ -56,7 +66,7 @@ def columns(channels=(), link=True, drift=False, hull=False, midline=False, perc
     return cols + (list(LINK_COLUMNS) if link else []) + (list(DRIFT_COLUMNS) if drift else []) + \
         (list(HULL_COLUMNS) if hull else []) + (list(MIDLINE_COLUMNS) if midline else []) + \
         [name.format(p=int(q), c=int(c)) for name in (PERCENTILE_COLUMNS if percentiles else ()) for c in channels
-         for q in percentiles]
+         for q in percentiles] + (list(NEIGHBOR_COLUMNS) if neighbors else [])
 
 
 def _device(device=None):
@@ -462,6 +472,114 @@ def link_raw(lab, pix, off, table_cap=None, shift=None):
     return pred, ovl
 
 
+def check_neighbors(r):
+    """the rule of ``measure_cells(neighbors=...)``, ``InferWorker.neighbors`` and --neighbors: None, or an int in 1 ..
+    MAX_NEIGHBOR_RADIUS"""
+    if r is None:
+        return None
+    try:
+        ok = not isinstance(r, (bool, str, bytes)) and int(r) == r and 1 <= int(r) <= MAX_NEIGHBOR_RADIUS
+    except (TypeError, ValueError, OverflowError):
+        ok = False
+    if not ok:
+        raise ValueError(f"neighbors: None or a whole number of pixels in 1 .. {MAX_NEIGHBOR_RADIUS} expected, got {r!r}")
+    return int(r)
+
+
+def _neighbors_call(lab, pix, off, radius, cap, pair_cap):
+    """one ``mseg_cell_neighbors`` call with room for ``pair_cap`` rows, repeated with the exact count if there are more
+    -> (ints int64 [9, n], pairs int32 [m, 5], status int32 [T])"""
+    lib = _lib.load()
+    dev = lab.device
+    T, H, W = (int(v) for v in lab.shape)
+    n = int(off[-1])
+    off_d = torch.from_numpy(np.array(off, np.int64)).to(dev)
+    nbytes = lib.mseg_cell_neighbors_workspace_bytes(T, n, cap)
+    if nbytes == 0:
+        raise ValueError(f"mseg_cell_neighbors: no workspace for T = {T}, {n} cells, table {cap}")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    out = torch.zeros((9, max(n, 1)), dtype=torch.int64, device=dev)
+    tail = torch.zeros(1 + (T + 1) // 2, dtype=torch.int64, device=dev)      # n_pairs, then the T status words: one download
+    while True:
+        rows = torch.zeros((max(pair_cap, 1), 5), dtype=torch.int32, device=dev)
+        _lib.check(lib.mseg_cell_neighbors(lab.data_ptr(), pix, T, H, W, off_d.data_ptr(), n, int(radius), int(cap),
+                                           out.data_ptr(), rows.data_ptr(), int(pair_cap), tail.data_ptr(),
+                                           tail.data_ptr() + 8, ws.data_ptr(), ws.numel(), _stream(dev)), "cell_neighbors")
+        host = tail.cpu().numpy()
+        m, status = int(host[0]), host[1:].view(np.int32)[:T].copy()
+        if m <= pair_cap:
+            return out.cpu().numpy()[:, :n], rows.cpu().numpy()[:m], status
+        pair_cap = m
+
+
+def neighbors_raw(lab, pix, off, radius, table_cap=None):
+    """``mseg_cell_neighbors`` for the whole stack -> (ints int64 [9, n], pairs int32 [m, 5]) on the host: per cell slot
+    contact_edges, border_edges, free_edges, n_touch, n_near, nn_label, nn_d2, contact_label, contact_label_edges, zeros for
+    absent ids; per pair of cells of one frame within ``radius`` a row frame, a, b, edges, d2 with a < b, sorted by (frame, a,
+    b).  The pair tables start at 8 entries per cell of the largest frame; a frame whose table filled up (the device status
+    word says so) is redone on its own with the table doubled until it is clean, at most up to more than K (K - 1) / 2
+    entries, which cannot fill up: the result is always exact."""
+    T = int(lab.shape[0])
+    n = int(off[-1])
+    radius = check_neighbors(radius)
+    if radius is None:
+        raise ValueError("neighbors_raw: a radius is needed")
+    if n == 0:
+        return np.zeros((9, 0), np.int64), np.zeros((0, 5), np.int32)
+    k = np.diff(np.asarray(off, np.int64))
+    if table_cap is None:
+        table_cap = max(MIN_TABLE, _pow2(8 * int(k.max())))
+    ints, pairs, status = _neighbors_call(lab, pix, off, radius, int(table_cap), 8 * n)
+    ints, parts = ints.copy(), [pairs[~np.isin(pairs[:, 0], np.nonzero(status)[0])]]
+    for t in np.nonzero(status)[0]:
+        kt = int(k[t])
+        top = max(MIN_TABLE, _pow2(kt * (kt - 1) // 2 + 1))
+        sub, cap = np.array([0, kt], np.int64), int(table_cap)
+        while True:
+            cap *= 2
+            if cap > top:
+                raise RuntimeError("mseg_cell_neighbors: a table of more than K (K - 1) / 2 entries reported full")
+            i2, p2, s2 = _neighbors_call(lab[t:t + 1], pix, sub, radius, cap, 8 * kt)
+            if not s2.any():
+                break
+        ints[:, off[t]:off[t + 1]] = i2
+        p2 = p2.copy()
+        p2[:, 0] = t
+        parts.append(p2)
+    pairs = np.concatenate(parts)
+    return ints, pairs[np.lexsort((pairs[:, 2], pairs[:, 1], pairs[:, 0]))]
+
+
+def cell_contacts(mask, radius=8, device=None):
+    """ The contact graph of a segmented stack: one row per pair of cells of one frame that lie within ``radius`` pixels of
+    each other, sorted by (frame, label_a, label_b), label_a < label_b.
+
+    ``contact``: the unit pixel edges the two cells share (0: they do not touch, or only at a corner); ``distance``: the
+    smallest distance between the centres of a pixel of the one and a pixel of the other (1 for cells that share an edge,
+    sqrt(2) for a corner; distance - 1 is the gap).  From the device (``mseg_cell_neighbors``), through ``neighbors_raw``
+    like ``measure_cells(neighbors=radius)``.  Whole pixels, centre-to-centre: no sub-pixel contour, no pairs beyond
+    ``radius`` (1 .. 32), no Voronoi or Delaunay neighbourhood.
+    :return: pandas.DataFrame with the columns CONTACT_COLUMNS.
+    """
+    radius = check_neighbors(radius)
+    if radius is None:
+        raise ValueError("cell_contacts: a radius in 1 .. 32 is needed")
+    dev = _device(device)
+    with torch.cuda.device(dev):
+        lab, pix = _labels_to_device(mask, dev)
+        off = np.zeros(int(lab.shape[0]) + 1, np.int64)
+        np.cumsum(_frame_counts(lab), out=off[1:])
+        pairs = neighbors_raw(lab, pix, off, radius)[1]
+    return contacts_from_pairs(pairs)
+
+
+def contacts_from_pairs(pairs):
+    """the DataFrame of ``cell_contacts`` from the sorted pair rows of ``neighbors_raw``: distance = sqrt(d2), fp64"""
+    pairs = np.asarray(pairs, np.int64).reshape(-1, 5)
+    return pd.DataFrame({"frame": pairs[:, 0], "label_a": pairs[:, 1], "label_b": pairs[:, 2], "contact": pairs[:, 3],
+                         "distance": np.sqrt(pairs[:, 4].astype(np.float64))}, columns=CONTACT_COLUMNS)
+
+
 def assemble_tracks(frame, label, pred, overlap, min_overlap=1):
     """ Track ids from overlap links; pure host code, O(cells).
 
@@ -532,8 +650,16 @@ def _midline(area, m):
     return [skel_n, chain, n_end, n_branch, length, area / length, y0, x0, y1, x1]
 
 
+def _neighborhood(v):
+    """the neighbourhood columns of one cell from the nine integers of ``mseg_cell_neighbors`` (NEIGHBOR_COLUMNS order)"""
+    contact, border, free, n_touch, n_near, nn_label, nn_d2, contact_label, contact_max = v
+    dist = math.sqrt(nn_d2) if nn_label else float("nan")
+    return [contact, border, contact / (contact + border + free), n_touch, n_near, nn_label, dist, dist - 1, contact_label,
+            contact_max]
+
+
 def table_from_sums(off, H, W, raw, channels=(), links=None, min_overlap=1, shift=None, hull=None, midline=None,
-                    order_stats=None):
+                    order_stats=None, neighbors=None):
     """the DataFrame from the integer sums of ``measure_raw`` (and ``links`` = (pred, overlap) or None); host arithmetic in
     Python integers and fp64.  ``shift``: int [T, 2], the (dy, dx) of every frame against its predecessor the links were
     taken under (row 0 ignored), or None: with it the drift columns follow the link columns.  ``hull``: int [10, n], the
@@ -546,13 +672,21 @@ def table_from_sums(off, H, W, raw, channels=(), links=None, min_overlap=1, shif
     otherwise, midline_width = area / midline_length, and the two end points (0 where there are none).  ``order_stats``:
     (percentiles, values uint32 [2 P, C, n], bg_values uint32 [2 P, T, C]): the integers of ``order_stats_raw`` for the ranks
     of ``percentile_ranks`` (cell counts: raw["shape"][0], background counts: raw["bg_sums"][0]), or None: with it the table
-    ends with p{P}_ch{c} = ``percentile_value`` of the two order statistics, and bg_p{P}_ch{c} (NaN without background)"""
+    ends with p{P}_ch{c} = ``percentile_value`` of the two order statistics, and bg_p{P}_ch{c} (NaN without background).
+    ``neighbors``: int [9, n], the integers of ``neighbors_raw``, or None: with it the table ends with the neighbourhood
+    columns: contact_length = contact_edges, border_length = border_edges, contact_fraction = contact_edges / (contact_edges
+    + border_edges + free_edges), n_touching = n_touch, n_neighbors = n_near, nn_label, nn_distance = sqrt(nn_d2) and nn_gap =
+    nn_distance - 1 (both NaN where no cell lies within the radius, nn_label then 0), contact_label and contact_max =
+    contact_label_edges (both 0 where no cell shares an edge)"""
     off = np.asarray(off, np.int64)
     area = raw["shape"][0]
     pct = check_percentiles(order_stats[0]) if order_stats is not None else ()
     if pct and not len(channels):
         raise ValueError("percentiles are taken of an image's channels: none is measured")
-    rows = {c: [] for c in columns(channels, links is not None, shift is not None, hull is not None, midline is not None, pct)}
+    rows = {c: [] for c in columns(channels, links is not None, shift is not None, hull is not None, midline is not None, pct,
+                                   neighbors is not None)}
+    if neighbors is not None:
+        nbl = [[int(v) for v in plane] for plane in np.asarray(neighbors).reshape(9, len(area))]
     if pct:
         vals = np.asarray(order_stats[1]).reshape(2 * len(pct), len(channels), len(area))
         bgv = np.asarray(order_stats[2]).reshape(2 * len(pct), len(off) - 1, len(channels))
@@ -598,6 +732,8 @@ def table_from_sums(off, H, W, raw, channels=(), links=None, min_overlap=1, shif
             if pct:
                 vals += [cell_p[i][ci][s] for ci in range(len(channels)) for i in range(len(pct))]
                 vals += [bg_p[i][t][ci] for ci in range(len(channels)) for i in range(len(pct))]
+            if neighbors is not None:
+                vals += _neighborhood([plane[s] for plane in nbl])
             for c, v in zip(rows, vals):
                 rows[c].append(v)
     df = pd.DataFrame(rows, columns=list(rows))
@@ -609,7 +745,7 @@ def table_from_sums(off, H, W, raw, channels=(), links=None, min_overlap=1, shif
 
 
 def measure_cells(mask, img=None, channels=None, link=True, min_overlap=1, device=None, drift=None, hull=False,
-                  midline=False, percentiles=None):
+                  midline=False, percentiles=None, neighbors=None):
     """ One row per cell of a segmented stack, ordered by (frame, label).
 
     :param mask: label stack [T, H, W] (or one frame [H, W]): host array or device tensor (int16 holding uint16 bits, or
@@ -642,10 +778,21 @@ def measure_cells(mask, img=None, channels=None, link=True, min_overlap=1, devic
         pixel, a bright neighbour or debris in the background does not move.  Linear interpolation between the two nearest
         order statistics, as ``np.percentile`` does by default; the order statistics are exact integers from the device.
         Needs ``img`` and at least one measured channel.
-    :return: pandas.DataFrame with the columns of ``columns(channels, link, drift is not None, hull, midline, percentiles)``.
+    :param neighbors: None (default): off.  R, a whole number in 1 .. 32: the table ends with every cell's neighbourhood
+        within its frame (NEIGHBOR_COLUMNS): contact_length, the unit pixel edges it shares with other cells, border_length,
+        those on the frame's border, contact_fraction, the first over all its exposed edges (= ``perimeter`` of ``hull``),
+        n_touching, the cells it shares an edge with, n_neighbors, the cells with a pixel within R pixels of one of its own,
+        nn_label / nn_distance / nn_gap, the nearest of them (ties to the smaller label; NaN and 0 if there is none within
+        R) and contact_label / contact_max, the cell it shares the most edges with.  Whole pixels only: distances are
+        centre-to-centre distances of pixels (two cells that share an edge are 1 apart, gap 0), no sub-pixel contour is
+        fitted, no neighbour beyond R is seen, and this is no Voronoi or Delaunay neighbourhood.  ``cell_contacts`` gives the
+        pairs themselves.  Needs neither ``link``, ``hull`` nor ``img``.
+    :return: pandas.DataFrame with the columns of ``columns(channels, link, drift is not None, hull, midline, percentiles,
+        neighbors is not None)``.
     """
     drift = check_drift(drift)
     percentiles = check_percentiles(percentiles)
+    neighbors = check_neighbors(neighbors)
     if percentiles and img is None:
         raise ValueError("percentiles are taken of an image's channels: no image given")
     if drift is not None and not link:
@@ -678,7 +825,8 @@ def measure_cells(mask, img=None, channels=None, link=True, min_overlap=1, devic
             ranks = percentile_ranks(raw["shape"][0].astype(np.int64), percentiles)[0]
             bg_ranks = percentile_ranks(raw["bg_sums"][0, :, 0].astype(np.int64), percentiles)[0]
             stats = (percentiles,) + order_stats_raw(lab, pix, off, image, channels, raw["bbox"], ranks, bg_ranks)
-    return table_from_sums(off, H, W, raw, channels, links, min_overlap, shift, outline, skel, stats)
+        near = neighbors_raw(lab, pix, off, neighbors)[0] if neighbors is not None else None
+    return table_from_sums(off, H, W, raw, channels, links, min_overlap, shift, outline, skel, stats, near)
 
 
 def write_cells(df, csv_path):

@@ -106,6 +106,10 @@ class InferWorker(QObject):
     # percentiles (50 = the median) of every cell's pixel values and of every frame's background per measured channel
     # (order statistics from the device; inference/cells.py)
     percentiles = None
+    # [extension] cell_table: None = off; R, a whole number in 1 .. 32: the table ends with every cell's neighbourhood within
+    # R pixels (contact edges, touching cells, nearest neighbour; contact_table gives the pairs; whole pixels, nothing beyond
+    # R; inference/cells.py)
+    neighbors = None
     # [extension] test-time augmentation (inference/tta.py): 1 = off (no existing route changes), 2 / 4 / 8 =
     # every frame is predicted under that many flips / rotations, the predictions are mapped back and averaged (fp32, in
     # member order) and the average is segmented: K network forwards per frame.  Whole-frame inference only
@@ -885,16 +889,23 @@ class InferWorker(QObject):
         (numbers of the source image, they name the columns) are measured.  Overlap linking: no motion model, no gap
         closing; with ``self.drift`` set, under the estimated stage drift of every frame pair; with ``self.hull`` set, with
         the outline columns; with ``self.midline`` set, with the midline columns; with ``self.percentiles`` set, with the
-        percentile columns. """
+        percentile columns; with ``self.neighbors`` set, with the neighbourhood columns. """
         from .cells import measure_cells
         df = measure_cells(results, img, link=True, min_overlap=self.min_overlap, device=self.device, drift=self.drift,
-                           hull=self.hull, midline=self.midline, percentiles=self.percentiles)
+                           hull=self.hull, midline=self.midline, percentiles=self.percentiles, neighbors=self.neighbors)
         if img is not None and channels is not None:      # the view holds the chosen channels only: name them by source
             names = {f'{k}_ch{i}': f'{k}_ch{int(c)}' for i, c in reversed(list(enumerate(channels)))
                      for k in ('mean', 'std', 'min', 'max', 'sum', 'bg_mean') +
                      tuple(f'{b}p{int(q)}' for q in (self.percentiles or ()) for b in ('', 'bg_'))}
             df = df.rename(columns=names)
         return df
+
+    def contact_table(self, results):
+        """ [extension] The contact graph of a segmented stack (inference/cells.py ``cell_contacts``): one row per pair of
+        cells of one frame within ``self.neighbors`` pixels of each other, with the pixel edges they share and their
+        distance.  Whole pixels, centre-to-centre; nothing beyond that radius. """
+        from .cells import cell_contacts
+        return cell_contacts(results, self.neighbors, self.device)
 
     def save_results(self, results_array, image_name, result_path=None, with_rois=False):
         """ ``<result_path>/<image stem>_channel<c>.tif`` (uint16 [T, H, W], the reference's local-save route) and, with
