@@ -122,7 +122,8 @@ typedef struct MsegKernelInfo {
   int32_t reserved0;
 } MsegKernelInfo;
 int mseg_igemm_query(const MsegIgemm* p, MsegKernelInfo* info);
-/* name of the main kernel of this thread's last mseg_igemm / mseg_wgrad call ("" before the first) */
+/* name of the main kernel of this thread's last mseg_igemm / mseg_wgrad / mseg_first_conv_fwd / mseg_first_conv_fwd_raw /
+ * mseg_first_wgrad call that launched ("" before the first; a refused call leaves it as it was) */
 const char* mseg_last_kernel(void);
 /* round-to-nearest-even conversion of n floats to bf16 (the packed weights of a MSEG_PREC_BF16 launch) */
 int mseg_f32_to_bf16(const float* src, uint16_t* dst, size_t n, void* stream);

@@ -355,8 +355,11 @@ static bool first_shape_ok(int N, int H, int W, int Cin, int Cout) {
          (256 % (Cout >> 2)) == 0;
 }
 
-extern "C" int mseg_first_conv_fwd(const float* x4, const float* w, const float* bias, int N, int H, int W, int Cin,
-                                   int Cout, void* z, int z_dtype, void* stream) {
+// The three entries below launch through MSEG_KL / MSEG_KL_AUX (common.h) between mseg_dispatch_begin(0) and
+// mseg_dispatch_end(nullptr), as mseg_igemm does: mseg_last_kernel() names the form a call took, e.g.
+// "first_conv_fwd_rows_kernel<false, true>".  The reduction behind the weight gradient is a helper (AUX).
+static int first_conv_fwd_dispatch(const float* x4, const float* w, const float* bias, int N, int H, int W, int Cin,
+                                  int Cout, void* z, int z_dtype, void* stream) {
   if (!x4 || !w || !z || !first_shape_ok(N, H, W, Cin, Cout)) return MSEG_EINVAL;
   if (z_dtype != MSEG_ST_F32 && z_dtype != MSEG_ST_BF16) return MSEG_EINVAL;
   const long long P = (long long)N * H * W;
@@ -365,9 +368,9 @@ extern "C" int mseg_first_conv_fwd(const float* x4, const float* w, const float*
     const dim3 grid((unsigned)((W + XS - 1) / XS), (unsigned)((H + FR_ROWS - 1) / FR_ROWS), (unsigned)N);
     const RawFrame none = {};
     if (z_dtype == MSEG_ST_BF16)
-      hipLaunchKernelGGL((first_conv_fwd_rows_kernel<true, false>), grid, dim3(256), 0, (hipStream_t)stream, x4, w, bias, H, W, Cout, z, none);
+      MSEG_KL((first_conv_fwd_rows_kernel<true, false>), grid, dim3(256), 0, (hipStream_t)stream, x4, w, bias, H, W, Cout, z, none);
     else
-      hipLaunchKernelGGL((first_conv_fwd_rows_kernel<false, false>), grid, dim3(256), 0, (hipStream_t)stream, x4, w, bias, H, W, Cout, z, none);
+      MSEG_KL((first_conv_fwd_rows_kernel<false, false>), grid, dim3(256), 0, (hipStream_t)stream, x4, w, bias, H, W, Cout, z, none);
     MSEG_LAUNCH_CHECK();
     return MSEG_OK;
   }
@@ -375,13 +378,21 @@ extern "C" int mseg_first_conv_fwd(const float* x4, const float* w, const float*
   long long blocks = (P + ppb - 1) / ppb;
   if (blocks > 8192) blocks = 8192;
   if (Cin == 1)
-    hipLaunchKernelGGL((first_conv_fwd_kernel<1>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x4, w, bias,
-                       N, H, W, Cin, Cout, z, z_dtype);
+    MSEG_KL((first_conv_fwd_kernel<1>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x4, w, bias, N, H, W,
+            Cin, Cout, z, z_dtype);
   else
-    hipLaunchKernelGGL((first_conv_fwd_kernel<4>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x4, w, bias,
-                       N, H, W, Cin, Cout, z, z_dtype);
+    MSEG_KL((first_conv_fwd_kernel<4>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x4, w, bias, N, H, W,
+            Cin, Cout, z, z_dtype);
   MSEG_LAUNCH_CHECK();
   return MSEG_OK;
+}
+
+extern "C" int mseg_first_conv_fwd(const float* x4, const float* w, const float* bias, int N, int H, int W, int Cin,
+                                   int Cout, void* z, int z_dtype, void* stream) {
+  mseg_dispatch_begin(0);
+  const int rc = first_conv_fwd_dispatch(x4, w, bias, N, H, W, Cin, Cout, z, z_dtype, stream);
+  mseg_dispatch_end(nullptr);
+  return rc;
 }
 
 static int raw_frame_check(const void* raw, int dtype, int H0, int W0, int pad_top, int pad_left, const uint32_t* minmax) {
@@ -425,9 +436,9 @@ extern "C" int mseg_frame_normalize(const void* raw, int dtype, int H0, int W0, 
   return mseg_frames_normalize(raw, dtype, 1, H0, W0, pad_top, pad_left, minmax, out, stream);
 }
 
-extern "C" int mseg_first_conv_fwd_raw(const void* raw, int dtype, int H0, int W0, int pad_top, int pad_left,
-                                       const uint32_t* minmax, const float* w, const float* bias, int Cout, void* z,
-                                       int z_dtype, void* stream) {
+static int first_conv_fwd_raw_dispatch(const void* raw, int dtype, int H0, int W0, int pad_top, int pad_left,
+                                      const uint32_t* minmax, const float* w, const float* bias, int Cout, void* z,
+                                      int z_dtype, void* stream) {
   if (raw_frame_check(raw, dtype, H0, W0, pad_top, pad_left, minmax) || !w || !z) return MSEG_EINVAL;
   if (z_dtype != MSEG_ST_F32 && z_dtype != MSEG_ST_BF16) return MSEG_EINVAL;
   const int H = H0 + pad_top, W = W0 + pad_left;
@@ -436,13 +447,23 @@ extern "C" int mseg_first_conv_fwd_raw(const void* raw, int dtype, int H0, int W
   const int XS = 256 / (Cout >> 3);
   const dim3 grid((unsigned)((W + XS - 1) / XS), (unsigned)((H + FR_ROWS - 1) / FR_ROWS), 1u);
   if (z_dtype == MSEG_ST_BF16)
-    hipLaunchKernelGGL((first_conv_fwd_rows_kernel<true, true>), grid, dim3(256), 0, (hipStream_t)stream, (const float*)nullptr, w,
-                       bias, H, W, Cout, z, f);
+    MSEG_KL((first_conv_fwd_rows_kernel<true, true>), grid, dim3(256), 0, (hipStream_t)stream, (const float*)nullptr, w,
+            bias, H, W, Cout, z, f);
   else
-    hipLaunchKernelGGL((first_conv_fwd_rows_kernel<false, true>), grid, dim3(256), 0, (hipStream_t)stream, (const float*)nullptr, w,
-                       bias, H, W, Cout, z, f);
+    MSEG_KL((first_conv_fwd_rows_kernel<false, true>), grid, dim3(256), 0, (hipStream_t)stream, (const float*)nullptr, w,
+            bias, H, W, Cout, z, f);
   MSEG_LAUNCH_CHECK();
   return MSEG_OK;
+}
+
+extern "C" int mseg_first_conv_fwd_raw(const void* raw, int dtype, int H0, int W0, int pad_top, int pad_left,
+                                       const uint32_t* minmax, const float* w, const float* bias, int Cout, void* z,
+                                       int z_dtype, void* stream) {
+  mseg_dispatch_begin(0);
+  const int rc = first_conv_fwd_raw_dispatch(raw, dtype, H0, W0, pad_top, pad_left, minmax, w, bias, Cout, z, z_dtype,
+                                             stream);
+  mseg_dispatch_end(nullptr);
+  return rc;
 }
 
 extern "C" size_t mseg_first_wgrad_workspace_bytes(int N, int H, int W, int Cout) {
@@ -452,7 +473,7 @@ extern "C" size_t mseg_first_wgrad_workspace_bytes(int N, int H, int W, int Cout
   return (size_t)blocks * 9 * Cout * sizeof(float);
 }
 
-extern "C" int mseg_first_wgrad(const float* x4, const void* dz, int dz_dtype, int N, int H, int W, int Cout, float* dW,
+static int first_wgrad_dispatch(const float* x4, const void* dz, int dz_dtype, int N, int H, int W, int Cout, float* dW,
                                 void* ws, void* stream) {
   if (!x4 || !dz || !dW || !ws || !first_shape_ok(N, H, W, 1, Cout)) return MSEG_EINVAL;
   if (dz_dtype != MSEG_ST_F32 && dz_dtype != MSEG_ST_BF16) return MSEG_EINVAL;
@@ -464,20 +485,28 @@ extern "C" int mseg_first_wgrad(const float* x4, const void* dz, int dz_dtype, i
   if (units > 0 && units <= 0x7fffffffLL) {
     const unsigned g = (unsigned)(units < blocks ? units : blocks);   // part[] rows beyond g stay unused: reduce over g
     if (dz_dtype == MSEG_ST_BF16)
-      hipLaunchKernelGGL((first_wgrad_rows_kernel<true>), dim3(g), dim3(256), 0, st, x4, dz, N, H, W, Cout, (float*)ws);
+      MSEG_KL((first_wgrad_rows_kernel<true>), dim3(g), dim3(256), 0, st, x4, dz, N, H, W, Cout, (float*)ws);
     else
-      hipLaunchKernelGGL((first_wgrad_rows_kernel<false>), dim3(g), dim3(256), 0, st, x4, dz, N, H, W, Cout, (float*)ws);
+      MSEG_KL((first_wgrad_rows_kernel<false>), dim3(g), dim3(256), 0, st, x4, dz, N, H, W, Cout, (float*)ws);
     MSEG_LAUNCH_CHECK();
-    hipLaunchKernelGGL(first_wgrad_reduce_kernel, dim3((9 * Cout + 7) / 8), dim3(256), 0, st, (const float*)ws, (int)g,
-                       Cout, dW);
+    MSEG_KL_AUX(first_wgrad_reduce_kernel, dim3((9 * Cout + 7) / 8), dim3(256), 0, st, (const float*)ws, (int)g, Cout,
+                dW);
     MSEG_LAUNCH_CHECK();
     return MSEG_OK;
   }
-  hipLaunchKernelGGL(first_wgrad_kernel, dim3((unsigned)blocks), dim3(256), 0, st, x4, dz, dz_dtype, N, H, W, Cout,
-                     per, (float*)ws);
+  MSEG_KL(first_wgrad_kernel, dim3((unsigned)blocks), dim3(256), 0, st, x4, dz, dz_dtype, N, H, W, Cout, per,
+          (float*)ws);
   MSEG_LAUNCH_CHECK();
-  hipLaunchKernelGGL(first_wgrad_reduce_kernel, dim3((9 * Cout + 7) / 8), dim3(256), 0, st, (const float*)ws, blocks,
-                     Cout, dW);
+  MSEG_KL_AUX(first_wgrad_reduce_kernel, dim3((9 * Cout + 7) / 8), dim3(256), 0, st, (const float*)ws, blocks, Cout,
+              dW);
   MSEG_LAUNCH_CHECK();
   return MSEG_OK;
+}
+
+extern "C" int mseg_first_wgrad(const float* x4, const void* dz, int dz_dtype, int N, int H, int W, int Cout, float* dW,
+                                void* ws, void* stream) {
+  mseg_dispatch_begin(0);
+  const int rc = first_wgrad_dispatch(x4, dz, dz_dtype, N, H, W, Cout, dW, ws, stream);
+  mseg_dispatch_end(nullptr);
+  return rc;
 }
