@@ -722,6 +722,40 @@ int mseg_cell_neighbors(const void* labels, int dtype, int T, int H, int W, cons
                         int radius, int64_t table_cap, int64_t* out, int32_t* pairs, int64_t pair_cap, int64_t* n_pairs,
                         int32_t* status, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- per-cell fluorescent foci (csrc/spots.hip) — an extension ---------------------------------------------
+ * labels, label_dtype, label_off, img, img_dtype, C and the four element strides as for mseg_cell_order_stats: the image is
+ * uint8 or uint16 and is read in place, whatever its strides.  For one channel plane v of one frame, scale = s in 1 .. 5 and
+ * threshold = thr in 1 .. 65535 grey levels:
+ *   B_k(v) = the separable smoothing with the binomial taps C(2k, j), j = 0 .. 2k, along rows, then along columns, in ONE
+ *            pass of 2k + 1 taps over the plane extended by its edge values (coordinates clamped); not normalised
+ *   D      = 16^s B_s(v) - B_2s(v): a difference of Gaussians (sigma = sqrt(s / 2) and sqrt(s)) in units of 16^(2s) per grey
+ *            level, exact in int64 (every term < 65535 * 16^10 < 2^56)
+ *   pixel p is a SPOT iff D(p) >= thr * 16^(2s) and, for each of its up to eight neighbours q inside the frame, D(p) > D(q),
+ *            or D(p) == D(q) and p comes before q in raster order.  Two 8-adjacent pixels are never both spots: a frame has
+ *            at most ceil(H / 2) * ceil(W / 2) spots per channel.
+ *   A spot belongs to the label under p: 0 is background; an id beyond the frame's table or a negative id is neither.
+ * mseg_cell_spots: outputs, all integers, written whole by the call, identical values from run to run:
+ *   cell_count  int32 [C][n_labels]   spots of channel c on cell slot s
+ *   bg_count    int32 [T][C]          spots of frame t and channel c on label 0
+ *   spots       MsegSpot [spot_cap]   one record per spot (whatever its label), in no particular order, zeros behind the last
+ *   n_spots     int64 [1] on the device: the spots of the whole call, always the full count; beyond spot_cap records nothing
+ *               is written (which spots are then written is unspecified).  spots == NULL with spot_cap == 0 is legal.
+ *   status      int32 [1] on the device; != 0: the list was too short (n_spots > spot_cap); the counts are valid all the same.
+ *   One workgroup per 32 x 64 tile of one frame and channel; the tile and a ring of 2s + 1 pixels in LDS.
+ *   ws >= mseg_cell_spots_workspace_bytes (256 bytes: the two tap rows; 0 = bad arguments).  MSEG_EINVAL: bad sizes, scale
+ *   outside 1 .. 5, threshold outside 1 .. 65535, C < 1, a dtype not listed, a NULL pointer where one is needed, H * W >=
+ *   2^31 - 512; MSEG_EWORKSPACE: ws_bytes too small; nothing is launched and nothing written on either.  n_labels == 0:
+ *   cell_count may be NULL, every spot is background or neither.                                                          */
+typedef struct MsegSpot {
+  int32_t frame, channel, y, x, label, value; /* value: the pixel's own value */
+  int64_t d;                                  /* D(p); the response in grey levels is d / 16^(2s) */
+} MsegSpot;
+size_t mseg_cell_spots_workspace_bytes(int T, int64_t n_labels, int C);
+int mseg_cell_spots(const void* labels, int label_dtype, int T, int H, int W, const int64_t* label_off, int64_t n_labels,
+                    const void* img, int img_dtype, int C, int64_t frame_stride, int64_t chan_stride, int64_t row_stride,
+                    int64_t pix_stride, int scale, int threshold, int32_t* cell_count, int32_t* bg_count, MsegSpot* spots,
+                    int64_t spot_cap, int64_t* n_spots, int32_t* status, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- training-set preparation (DataCropWorker src/utils/data_cropping.py:157-264,286,
  * DataImportWorker src/utils/data_import.py:125-194, DataExportWorker src/utils/data_export.py:100-101) -----------------
  * mseg_frame_stats: out[4] (device) = {min, max, sum v, sum v^2} of one uint8 / uint16 frame, exact, one pass (replaces

@@ -14,7 +14,8 @@ the GUI's Export button (inference/result_export.py) for the segmented channel o
 ``--hull`` with ``--cells``: perimeter, convex hull and Feret length / width / angle of every cell (inference/cells.py);
 ``--midline`` with ``--cells``: the thinned midline of every cell: its length, for bent and filamentous cells (inference/cells.py);
 ``--percentiles [P ...]`` with ``--cells``: percentiles (default 50, the median) of every cell's pixel values and of the background;
-``--neighbors [R]`` with ``--cells``: every cell's contacts and nearest neighbour within R pixels, and ``..._contacts.csv``, the pairs.
+``--neighbors [R]`` with ``--cells``: every cell's contacts and nearest neighbour within R pixels, and ``..._contacts.csv``, the pairs;
+``--spots THR [--spot_scale S]`` with ``--cells``: every cell's fluorescent foci of at least THR grey levels, and ``..._spots.csv``, the spots.
 """
 import argparse
 from pathlib import Path
@@ -106,6 +107,14 @@ class Parser(argparse.ArgumentParser):
                 ns.neighbors = check_neighbors(ns.neighbors)
             except ValueError as e:
                 self.error(f'--neighbors: {e}')
+        if ns.spots is not None:
+            if not ns.cells:
+                self.error('--spots needs --cells (it adds columns to the cell table)')
+            from microbeseg_amd.inference.cells import check_spots
+            try:
+                ns.spots, ns.spot_scale = check_spots(ns.spots, ns.spot_scale)
+            except ValueError as e:
+                self.error(f'--spots: {e}')
         if ns.scale != 1:
             if ns.tta > 1:
                 self.error('--scale and --tta > 1 cannot be combined')
@@ -205,6 +214,18 @@ def build_parser():
                              'stem>_contacts.csv, one row per pair of cells within R: frame, label_a, label_b, contact, '
                              'distance.  Whole pixels, centre-to-centre distances: no sub-pixel contour, nothing beyond R, no '
                              'Voronoi or Delaunay neighbourhood')
+    parser.add_argument('--spots', default=None, type=int, metavar='THR',
+                        help='[extension] with --cells: add every cell\'s fluorescent foci per measured channel: n_spots_ch{c}, '
+                             'the local maxima of an exact band-pass response (difference of two binomial smoothings) of at '
+                             'least THR grey levels (1 .. 65535) under the cell, spot_max_ch{c} / spot_sum_ch{c}, their '
+                             'largest and summed response, and bg_spots_ch{c}, the frame\'s spots on the background; also '
+                             'write <mask file stem>_spots.csv, one row per spot on a cell: frame, channel, label, y, x, '
+                             'value, response, axis_pos, axis_off (the position along and across the cell, +-1 = the poles; '
+                             'the sign of axis_pos is arbitrary).  Whole pixels, a fixed threshold: no sub-pixel fit, no '
+                             'automatic threshold, no linking of spots over time; uint8 / uint16 images')
+    parser.add_argument('--spot_scale', default=2, type=int, metavar='S',
+                        help='[extension] with --spots: the size of the foci, 1 .. 5 (default 2): the band-pass is the '
+                             'difference of Gaussians with sigma = sqrt(S / 2) and sqrt(S) pixels')
     return parser
 
 
@@ -250,6 +271,8 @@ def main():
     worker.midline = args.midline
     worker.percentiles = tuple(args.percentiles) if args.percentiles else None
     worker.neighbors = args.neighbors
+    worker.spots = args.spots
+    worker.spot_scale = args.spot_scale
     worker.tta = args.tta
     worker.scale = args.scale
     if args.drift is not None:
@@ -264,6 +287,9 @@ def main():
     if args.neighbors is not None:
         print(f'Cell table: with the neighbourhood of every cell within {args.neighbors} px (contacts, nearest neighbour); '
               'the pairs go to ..._contacts.csv')
+    if args.spots is not None:
+        print(f'Cell table: with the fluorescent foci of every cell (response >= {args.spots} grey levels at scale '
+              f'{args.spot_scale}); the spots go to ..._spots.csv')
     if args.scale != 1:
         print(f'Inference at {args.scale} x the resolution of the frames')
     if args.tta > 1:
@@ -303,9 +329,12 @@ def main():
             if view.dtype not in (np.uint8, np.uint16):
                 print(f'Skip intensity columns of {img_id.stem} (they need uint8 / uint16 images, got {view.dtype})')
                 view, channels = None, []
+            worker.spots = args.spots if view is not None else None      # the spot columns are intensity columns
             write_cells(worker.cell_table(results, view, channels), out_file.with_name(out_file.stem + '_cells.csv'))
             if args.neighbors is not None:
                 write_cells(worker.contact_table(results), out_file.with_name(out_file.stem + '_contacts.csv'))
+            if worker.spots is not None:
+                write_cells(worker.spot_table(results, view, channels), out_file.with_name(out_file.stem + '_spots.csv'))
     print('--- Finished ---')
 
 

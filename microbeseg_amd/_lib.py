@@ -195,6 +195,9 @@ SIGNATURES = {
                                    _P, _I, _P, _P, _P, _P, _P, _P, _SZ, _P]),
     "mseg_cell_neighbors_workspace_bytes": (_SZ, [_I, C.c_int64, C.c_int64]),
     "mseg_cell_neighbors": (_I, [_P, _I, _I, _I, _I, _P, C.c_int64, _I, C.c_int64, _P, _P, C.c_int64, _P, _P, _P, _SZ, _P]),
+    "mseg_cell_spots_workspace_bytes": (_SZ, [_I, C.c_int64, _I]),
+    "mseg_cell_spots": (_I, [_P, _I, _I, _I, _I, _P, C.c_int64, _P, _I, _I, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _I, _I,
+                             _P, _P, _P, C.c_int64, _P, _P, _P, _SZ, _P]),
     "mseg_frame_stats": (_I, [_P, _I, _SZ, _P, _P]),
     "mseg_crops_extract": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "mseg_crop_census_workspace_bytes": (_SZ, []),

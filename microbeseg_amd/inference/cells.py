@@ -23,7 +23,14 @@ every cell's NEIGHBOURHOOD within its frame: how many unit pixel edges it shares
 and with background, how many cells touch it, how many lie within R pixels, the nearest of them and the one it shares the
 most edges with (csrc/neighbors.hip: ``mseg_cell_neighbors``); ``cell_contacts`` returns the contact graph
 itself, one row per pair of cells within R.  Whole pixels only: distances are centre-to-centre distances of pixels, no
-sub-pixel contour is fitted, nothing beyond R is seen, and this is no Voronoi or Delaunay neighbourhood.
+sub-pixel contour is fitted, nothing beyond R is seen, and this is no Voronoi or Delaunay neighbourhood.  ``spots=THR`` adds
+every cell's fluorescent FOCI per measured channel: the local maxima of an exact integer band-pass of the image, D = 16^s
+B_s(v) - B_2s(v) with binomial smoothings B_k (a difference of Gaussians, s = ``spot_scale``), whose response reaches THR
+grey levels, counted under every cell and on the background (csrc/spots.hip: ``mseg_cell_spots``; DESIGN.md §6t);
+``cell_spots`` returns the spots themselves with their position along the cell's axes, which separates polar from mid-cell
+foci.  Integers from the device, one division per float here.  Whole pixels and a fixed threshold: no sub-pixel positions,
+no Gaussian fitting, no automatic or noise-relative threshold (the list carries the response: re-threshold afterwards), no
+float images, no linking of spots over time.
 """
 import ctypes as C
 import math
@@ -51,13 +58,20 @@ NEIGHBOR_COLUMNS = ['contact_length', 'border_length', 'contact_fraction', 'n_to
 CONTACT_COLUMNS = ['frame', 'label_a', 'label_b', 'contact', 'distance']
 MIN_TABLE = 64        # smallest pair table mseg_cell_links and mseg_cell_neighbors accept
 MAX_NEIGHBOR_RADIUS = 32   # largest radius mseg_cell_neighbors accepts
+SPOT_COLUMNS = ['n_spots_ch{c}', 'spot_max_ch{c}', 'spot_sum_ch{c}', 'bg_spots_ch{c}']      # channel by channel
+SPOT_TABLE_COLUMNS = ['frame', 'channel', 'label', 'y', 'x', 'value', 'response', 'axis_pos', 'axis_off']
+MAX_SPOT_SCALE = 5    # largest scale mseg_cell_spots accepts
+MAX_SPOT_THRESHOLD = 65535
+SPOT_RECORD = np.dtype([('frame', '<i4'), ('channel', '<i4'), ('y', '<i4'), ('x', '<i4'), ('label', '<i4'), ('value', '<i4'),
+                        ('d', '<i8')])      # MsegSpot
 
 
-def columns(channels=(), link=True, drift=False, hull=False, midline=False, percentiles=(), neighbors=False):
+def columns(channels=(), link=True, drift=False, hull=False, midline=False, percentiles=(), neighbors=False, spots=False):
     """the table's columns, in order, for the measured ``channels``; ``drift``: with the drift columns (needs ``link``);
     ``hull``: with the outline columns; ``midline``: with the midline columns; ``percentiles``: with p{P}_ch{c} for every
     measured channel (per channel the percentiles in the order given), then bg_p{P}_ch{c} likewise; ``neighbors``: with the
-    neighbourhood columns; these come last"""
+    neighbourhood columns; ``spots``: with the four spot columns of every measured channel, channel by channel; these come
+    last"""
     if drift and not link:
         raise ValueError("the drift columns belong to the link columns: drift needs link")
     cols = list(SHAPE_COLUMNS)
@@ -66,7 +80,8 @@ def columns(channels=(), link=True, drift=False, hull=False, midline=False, perc
     return cols + (list(LINK_COLUMNS) if link else []) + (list(DRIFT_COLUMNS) if drift else []) + \
         (list(HULL_COLUMNS) if hull else []) + (list(MIDLINE_COLUMNS) if midline else []) + \
         [name.format(p=int(q), c=int(c)) for name in (PERCENTILE_COLUMNS if percentiles else ()) for c in channels
-         for q in percentiles] + (list(NEIGHBOR_COLUMNS) if neighbors else [])
+         for q in percentiles] + (list(NEIGHBOR_COLUMNS) if neighbors else []) + \
+        [name.format(c=int(c)) for c in (channels if spots else ()) for name in SPOT_COLUMNS]
 
 
 def _device(device=None):
@@ -580,6 +595,189 @@ def contacts_from_pairs(pairs):
                          "distance": np.sqrt(pairs[:, 4].astype(np.float64))}, columns=CONTACT_COLUMNS)
 
 
+def check_spots(thr, scale=2):
+    """the rule of ``measure_cells(spots=..., spot_scale=...)``, ``InferWorker.spots`` / ``spot_scale`` and --spots /
+    --spot_scale: thr None = off -> None; else a whole number of grey levels in 1 .. 65535 and a whole scale in 1 .. 5 ->
+    (thr, scale) as ints"""
+    if thr is None:
+        return None
+    for name, v, top in (("spots", thr, MAX_SPOT_THRESHOLD), ("spot_scale", scale, MAX_SPOT_SCALE)):
+        try:
+            ok = not isinstance(v, (bool, str, bytes)) and int(v) == v and 1 <= int(v) <= top
+        except (TypeError, ValueError, OverflowError):
+            ok = False
+        if not ok:
+            raise ValueError(f"{name}: " + ("None or " if name == "spots" else "") + f"a whole number in 1 .. {top} expected, "
+                             f"got {v!r}")
+    return int(thr), int(scale)
+
+
+def spot_bound(T, H, W, C=1):
+    """the most spots T frames of H x W can have in C channels: two 8-adjacent pixels are never both spots"""
+    return int(T) * int(C) * ((int(H) + 1) // 2) * ((int(W) + 1) // 2)
+
+
+def spots_raw(lab, pix, off, image, channels, thr, scale, spot_cap=None):
+    """``mseg_cell_spots`` for the whole stack, one call per channel group -> (cell_count int32 [C, n], bg_count int32 [T, C],
+    records) on the host.  records: a SPOT_RECORD array, one entry per spot (frame, channel = the INDEX into ``channels``, y,
+    x, label, value = the pixel's own value, d = D(p) in units of 16^(2 scale) per grey level), sorted by (frame, channel, y,
+    x): the same bytes from run to run.  ``spot_cap``: room for so many spots per call (default: 4 per cell and 1024 per
+    frame and channel); a list that overflowed (the device's status word says so) is never returned: the call is redone
+    with room for the count the device reported, at most the worst case ``spot_bound``: the result is always complete."""
+    lib = _lib.load()
+    dev = lab.device
+    T, H, W = (int(v) for v in lab.shape)
+    n = int(off[-1])
+    if image is None or not len(channels):
+        raise ValueError("spots are taken of an image's channels: none given")
+    if check_spots(thr, scale) is None:
+        raise ValueError("spots_raw: a threshold is needed")
+    thr, scale = check_spots(thr, scale)
+    off_d = torch.from_numpy(np.ascontiguousarray(off, np.int64)).to(dev)
+    _, base, ipix, _, (fs, cs0, rs, ps) = image
+    counts, bgs, recs, first_ci = [], [], [], 0
+    for first, step, Cg in _channel_groups(list(channels)):
+        nbytes = lib.mseg_cell_spots_workspace_bytes(T, n, Cg)
+        if nbytes == 0:
+            raise ValueError(f"mseg_cell_spots: no workspace for T = {T}, {n} cells, {Cg} channels")
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        top = spot_bound(T, H, W, Cg)
+        cap = min(top, (4 * n + 1024 * T) * Cg) if spot_cap is None else max(int(spot_cap), 0)
+        while True:
+            tail = torch.zeros(2, dtype=torch.int64, device=dev)                      # n_spots, then the status word
+            ints = torch.zeros(Cg * n + T * Cg, dtype=torch.int32, device=dev)       # cell_count, then bg_count
+            lst = torch.zeros((max(cap, 1), 4), dtype=torch.int64, device=dev)       # 32 bytes per record
+            _lib.check(lib.mseg_cell_spots(lab.data_ptr(), pix, T, H, W, off_d.data_ptr(), n,
+                                           base + first * cs0 * (1 if ipix == _lib.PIX_U8 else 2), ipix, Cg, fs, step * cs0, rs,
+                                           ps, scale, thr, ints.data_ptr() if n else None, ints.data_ptr() + 4 * Cg * n,
+                                           lst.data_ptr() if cap else None, cap, tail.data_ptr(), tail.data_ptr() + 8,
+                                           ws.data_ptr(), ws.numel(), _stream(dev)), "cell_spots")
+            end = tail.cpu().numpy()
+            found, status = int(end[0]), int(end[1:].view(np.int32)[0])
+            if found > top:
+                raise RuntimeError(f"mseg_cell_spots: {found} spots reported, the frames can hold {top} at most")
+            if found <= cap and not status:
+                break
+            cap = found
+        host = ints.cpu().numpy()
+        counts.append(host[:Cg * n].reshape(Cg, n).copy())
+        bgs.append(host[Cg * n:Cg * n + T * Cg].reshape(T, Cg).copy())
+        r = lst.cpu().numpy().reshape(-1).view(SPOT_RECORD)[:found].copy()
+        r['channel'] += first_ci
+        recs.append(r)
+        first_ci += Cg
+    records = np.concatenate(recs)
+    return np.concatenate(counts, axis=0), np.concatenate(bgs, axis=1), \
+        records[np.lexsort((records['x'], records['y'], records['channel'], records['frame']))]
+
+
+def spot_axes(dy, dx, major, minor, orientation):
+    """(axis_pos, axis_off) of an offset (dy, dx) from a cell's centroid: its projections on the cell's major axis, the
+    direction (cos orientation, sin orientation) in (row, column), and on its minor axis, (-sin orientation, cos
+    orientation), divided by half the major and half the minor axis length; fp64, arrays or scalars.  NaN where the axis
+    length is 0.  The SIGN of axis_pos is arbitrary: a cell has no head.  The orientation is the table's own (``_axes``), with
+    its special case: a cell whose row and column variances are EXACTLY equal gets +-pi/4 by scikit-image 0.18.3's rule, which
+    for an exactly diagonal cell names the minor axis; axis_pos and axis_off then change places, as they would for anyone
+    who projects on the table's ``orientation`` column."""
+    dy, dx, o = np.asarray(dy, np.float64), np.asarray(dx, np.float64), np.asarray(orientation, np.float64)
+    major, minor = np.asarray(major, np.float64), np.asarray(minor, np.float64)
+    # the C library's cos / sin value by value: numpy's array loops may use other kernels for long arrays than for scalars
+    co = np.array([math.cos(v) for v in o.ravel().tolist()], np.float64).reshape(o.shape)
+    si = np.array([math.sin(v) for v in o.ravel().tolist()], np.float64).reshape(o.shape)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        pos = np.where(major > 0, (dy * co + dx * si) / (0.5 * major), np.nan)
+        offs = np.where(minor > 0, (dx * co - dy * si) / (0.5 * minor), np.nan)
+    return pos, offs
+
+
+def spots_from_records(records, scale, off, raw, channels, background=False):
+    """the DataFrame of ``cell_spots`` from the sorted records of ``spots_raw`` and the integer sums of ``measure_raw``:
+    response = d / 16^(2 scale) (int64 -> fp64 rounds to nearest and the division by a power of two is exact: the correctly
+    rounded quotient of the two integers); axis_pos / axis_off from the centroid, the orientation and the axis lengths the
+    table derives (``_axes``), NaN for label 0, for a label that is no cell of the frame, and for a zero axis"""
+    off = np.asarray(off, np.int64)
+    records = np.asarray(records, SPOT_RECORD)
+    if not background:
+        records = records[records['label'] != 0]
+    t, label = records['frame'].astype(np.int64), records['label'].astype(np.int64)
+    slot = off[t] + label - 1
+    area = np.asarray(raw["shape"][0]).astype(np.int64)
+    on_cell = (label >= 1) & (label <= off[t + 1] - off[t])
+    on_cell[on_cell] = area[slot[on_cell]] > 0
+    used, inverse = np.unique(slot[on_cell], return_inverse=True)
+    geo = np.zeros((len(used), 5), np.float64)                   # centroid_y, centroid_x, major, minor, orientation
+    for i, k in enumerate(used.tolist()):
+        n, sy, sx, syy, sxx, sxy = (int(plane[k]) for plane in raw["shape"])
+        geo[i] = (sy / n, sx / n) + _axes(n, sy, sx, syy, sxx, sxy)
+    g = geo[inverse]
+    pos, offs = np.full(len(records), np.nan), np.full(len(records), np.nan)
+    pos[on_cell], offs[on_cell] = spot_axes(records['y'][on_cell] - g[:, 0], records['x'][on_cell] - g[:, 1], g[:, 2], g[:, 3],
+                                            g[:, 4])
+    names = np.asarray([int(c) for c in channels], np.int64)
+    return pd.DataFrame({"frame": t, "channel": names[records['channel']], "label": label,
+                         "y": records['y'].astype(np.int64), "x": records['x'].astype(np.int64),
+                         "value": records['value'].astype(np.int64),
+                         "response": records['d'].astype(np.float64) / float(1 << (8 * int(scale))), "axis_pos": pos,
+                         "axis_off": offs}, columns=SPOT_TABLE_COLUMNS)
+
+
+def cell_spots(mask, img, channels=None, spots=None, spot_scale=2, background=False, device=None):
+    """ The fluorescent foci of a segmented stack: one row per spot, sorted by (frame, channel, y, x).
+
+    A spot is a local maximum of the exact integer band-pass D = 16^s B_s(v) - B_2s(v) of a channel plane (a difference of
+    Gaussians with sigma = sqrt(s / 2) and sqrt(s), s = ``spot_scale`` in 1 .. 5; csrc/spots.hip ``mseg_cell_spots``, DESIGN.md
+    §6t) whose response D / 16^(2 s) reaches ``spots`` grey levels (1 .. 65535); it belongs to the label under it.
+    ``value``: the pixel's own value; ``response``: in grey levels.  ``axis_pos`` / ``axis_off``: the spot's offset from its
+    cell's centroid, projected on the cell's major / minor axis and divided by half the ``major_axis_length`` / half the
+    ``minor_axis_length`` of the cell table: about +-1 at the poles, 0 at mid-cell.  NaN for label 0 and for a zero axis.  The
+    SIGN of axis_pos is arbitrary, because a cell has no head: only |axis_pos| separates polar from mid-cell foci.
+    ``channels``: indices into the channel axis of ``img`` (default: all); ``background=False`` drops the spots on label 0.
+    Whole pixels: no sub-pixel positions, no Gaussian fit; a fixed threshold in grey levels, no automatic or noise-relative
+    one (the list carries ``response``: re-threshold afterwards); uint8 / uint16 images only; spots are not linked over time.
+    :return: pandas.DataFrame with the columns SPOT_TABLE_COLUMNS.
+    """
+    checked = check_spots(spots, spot_scale)
+    if checked is None:
+        raise ValueError("cell_spots: a threshold in 1 .. 65535 grey levels is needed")
+    if img is None:
+        raise ValueError("spots are taken of an image's channels: no image given")
+    dev = _device(device)
+    with torch.cuda.device(dev):
+        lab, pix = _labels_to_device(mask, dev)
+        T, H, W = (int(v) for v in lab.shape)
+        off = np.zeros(T + 1, np.int64)
+        np.cumsum(_frame_counts(lab), out=off[1:])
+        image = _image_to_device(img, (T, H, W), dev)
+        if image is None:
+            raise ValueError("only uint8 / uint16 images are measured")
+        channels = list(range(image[3])) if channels is None else [int(c) for c in channels]
+        if any(c < 0 or c >= image[3] for c in channels):
+            raise ValueError(f"channels {channels} requested, the image has {image[3]}")
+        if not channels:
+            raise ValueError("spots are taken of an image's channels: none is measured")
+        raw = measure_raw(lab, pix, off)
+        records = spots_raw(lab, pix, off, image, channels, *checked)[2]
+    return spots_from_records(records, checked[1], off, raw, channels, background)
+
+
+def _spot_sums(records, off, n_channels):
+    """{(channel index, cell slot): (largest D, sum of D)} over the records on a cell of their frame.  The sums are exact:
+    the two 32-bit halves of D are added apart in int64 and joined in Python integers"""
+    off = np.asarray(off, np.int64)
+    records = np.asarray(records, SPOT_RECORD)
+    t, label, ci = records['frame'].astype(np.int64), records['label'].astype(np.int64), records['channel'].astype(np.int64)
+    ok = (label >= 1) & (label <= off[t + 1] - off[t]) & (ci >= 0) & (ci < n_channels)
+    n = int(off[-1])
+    keys, inverse = np.unique(ci[ok] * n + off[t[ok]] + label[ok] - 1, return_inverse=True)
+    d = records['d'][ok]
+    top = np.full(len(keys), np.iinfo(np.int64).min, np.int64)
+    lo, hi = np.zeros(len(keys), np.int64), np.zeros(len(keys), np.int64)
+    np.maximum.at(top, inverse, d)
+    np.add.at(lo, inverse, d & 0xFFFFFFFF)
+    np.add.at(hi, inverse, d >> 32)                            # arithmetic shift: d == (d >> 32 << 32) + (d & 0xFFFFFFFF)
+    return {(k // n, k % n): (m, (h << 32) + l) for k, m, l, h in zip(keys.tolist(), top.tolist(), lo.tolist(), hi.tolist())}
+
+
 def assemble_tracks(frame, label, pred, overlap, min_overlap=1):
     """ Track ids from overlap links; pure host code, O(cells).
 
@@ -659,7 +857,7 @@ def _neighborhood(v):
 
 
 def table_from_sums(off, H, W, raw, channels=(), links=None, min_overlap=1, shift=None, hull=None, midline=None,
-                    order_stats=None, neighbors=None):
+                    order_stats=None, neighbors=None, spots=None):
     """the DataFrame from the integer sums of ``measure_raw`` (and ``links`` = (pred, overlap) or None); host arithmetic in
     Python integers and fp64.  ``shift``: int [T, 2], the (dy, dx) of every frame against its predecessor the links were
     taken under (row 0 ignored), or None: with it the drift columns follow the link columns.  ``hull``: int [10, n], the
@@ -677,14 +875,25 @@ def table_from_sums(off, H, W, raw, channels=(), links=None, min_overlap=1, shif
     columns: contact_length = contact_edges, border_length = border_edges, contact_fraction = contact_edges / (contact_edges
     + border_edges + free_edges), n_touching = n_touch, n_neighbors = n_near, nn_label, nn_distance = sqrt(nn_d2) and nn_gap =
     nn_distance - 1 (both NaN where no cell lies within the radius, nn_label then 0), contact_label and contact_max =
-    contact_label_edges (both 0 where no cell shares an edge)"""
+    contact_label_edges (both 0 where no cell shares an edge).  ``spots``: (scale, cell_count int32 [C, n], bg_count int32
+    [T, C], records), the scale and the three results of ``spots_raw``, or None: with it the table ends with four columns per
+    measured channel: n_spots_ch{c} = cell_count, spot_max_ch{c} = the largest D among the cell's records / 16^(2 scale) (NaN
+    without a spot), spot_sum_ch{c} = the exact integer sum of their D / 16^(2 scale) (0 without), bg_spots_ch{c} = bg_count
+    of the frame"""
     off = np.asarray(off, np.int64)
     area = raw["shape"][0]
     pct = check_percentiles(order_stats[0]) if order_stats is not None else ()
     if pct and not len(channels):
         raise ValueError("percentiles are taken of an image's channels: none is measured")
+    if spots is not None and not len(channels):
+        raise ValueError("spots are taken of an image's channels: none is measured")
     rows = {c: [] for c in columns(channels, links is not None, shift is not None, hull is not None, midline is not None, pct,
-                                   neighbors is not None)}
+                                   neighbors is not None, spots is not None)}
+    if spots is not None:
+        sp_unit = 1 << (8 * int(spots[0]))
+        sp_n = np.asarray(spots[1]).reshape(len(channels), len(area)).tolist()
+        sp_bg = np.asarray(spots[2]).reshape(len(off) - 1, len(channels)).tolist()
+        sp_acc = _spot_sums(spots[3], off, len(channels))
     if neighbors is not None:
         nbl = [[int(v) for v in plane] for plane in np.asarray(neighbors).reshape(9, len(area))]
     if pct:
@@ -734,6 +943,10 @@ def table_from_sums(off, H, W, raw, channels=(), links=None, min_overlap=1, shif
                 vals += [bg_p[i][t][ci] for ci in range(len(channels)) for i in range(len(pct))]
             if neighbors is not None:
                 vals += _neighborhood([plane[s] for plane in nbl])
+            if spots is not None:
+                for ci in range(len(channels)):
+                    top, total = sp_acc.get((ci, s), (None, 0))
+                    vals += [sp_n[ci][s], top / sp_unit if top is not None else float("nan"), total / sp_unit, sp_bg[t][ci]]
             for c, v in zip(rows, vals):
                 rows[c].append(v)
     df = pd.DataFrame(rows, columns=list(rows))
@@ -745,7 +958,7 @@ def table_from_sums(off, H, W, raw, channels=(), links=None, min_overlap=1, shif
 
 
 def measure_cells(mask, img=None, channels=None, link=True, min_overlap=1, device=None, drift=None, hull=False,
-                  midline=False, percentiles=None, neighbors=None):
+                  midline=False, percentiles=None, neighbors=None, spots=None, spot_scale=2):
     """ One row per cell of a segmented stack, ordered by (frame, label).
 
     :param mask: label stack [T, H, W] (or one frame [H, W]): host array or device tensor (int16 holding uint16 bits, or
@@ -787,14 +1000,27 @@ def measure_cells(mask, img=None, channels=None, link=True, min_overlap=1, devic
         centre-to-centre distances of pixels (two cells that share an edge are 1 apart, gap 0), no sub-pixel contour is
         fitted, no neighbour beyond R is seen, and this is no Voronoi or Delaunay neighbourhood.  ``cell_contacts`` gives the
         pairs themselves.  Needs neither ``link``, ``hull`` nor ``img``.
+    :param spots: None (default): off.  THR, a whole number of grey levels in 1 .. 65535: the table ends with every cell's
+        fluorescent FOCI in every measured channel (SPOT_COLUMNS): n_spots_ch{c}, the local maxima of the band-pass response
+        (``cell_spots``; csrc/spots.hip) of at least THR grey levels under the cell, spot_max_ch{c} and
+        spot_sum_ch{c}, the largest and the sum of their responses (NaN and 0 without a spot), and bg_spots_ch{c}, the
+        frame's spots on label 0 (the same for all rows of a frame: how many detections to expect by chance).
+        ``cell_spots`` gives the spots themselves, with their position along the cell.  Whole pixels, a fixed threshold: no
+        sub-pixel positions or Gaussian fits, no automatic or noise-relative threshold, uint8 / uint16 images only, no
+        linking of spots over time.  Needs ``img`` and at least one measured channel.
+    :param spot_scale: s, a whole number in 1 .. 5 (default 2): the band-pass is the difference of two binomial smoothings
+        with sigma = sqrt(s / 2) and sqrt(s) pixels: foci of about that radius answer best.  Read only with ``spots``.
     :return: pandas.DataFrame with the columns of ``columns(channels, link, drift is not None, hull, midline, percentiles,
-        neighbors is not None)``.
+        neighbors is not None, spots is not None)``.
     """
     drift = check_drift(drift)
     percentiles = check_percentiles(percentiles)
     neighbors = check_neighbors(neighbors)
+    spots = check_spots(spots, spot_scale)
     if percentiles and img is None:
         raise ValueError("percentiles are taken of an image's channels: no image given")
+    if spots is not None and img is None:
+        raise ValueError("spots are taken of an image's channels: no image given")
     if drift is not None and not link:
         raise ValueError("drift changes how cells are linked: it needs link=True")
     dev = _device(device)
@@ -815,6 +1041,8 @@ def measure_cells(mask, img=None, channels=None, link=True, min_overlap=1, devic
             channels = []
         if percentiles and not channels:
             raise ValueError("percentiles are taken of an image's channels: none is measured")
+        if spots is not None and not channels:
+            raise ValueError("spots are taken of an image's channels: none is measured")
         raw = measure_raw(lab, pix, off, image, channels)
         shift = pick_drift(drift_raw(lab, pix, off, drift)) if drift is not None else None
         links = link_raw(lab, pix, off, shift=shift) if link else None
@@ -826,7 +1054,8 @@ def measure_cells(mask, img=None, channels=None, link=True, min_overlap=1, devic
             bg_ranks = percentile_ranks(raw["bg_sums"][0, :, 0].astype(np.int64), percentiles)[0]
             stats = (percentiles,) + order_stats_raw(lab, pix, off, image, channels, raw["bbox"], ranks, bg_ranks)
         near = neighbors_raw(lab, pix, off, neighbors)[0] if neighbors is not None else None
-    return table_from_sums(off, H, W, raw, channels, links, min_overlap, shift, outline, skel, stats, near)
+        foci = (spots[1],) + spots_raw(lab, pix, off, image, channels, *spots) if spots is not None else None
+    return table_from_sums(off, H, W, raw, channels, links, min_overlap, shift, outline, skel, stats, near, foci)
 
 
 def write_cells(df, csv_path):

@@ -110,6 +110,11 @@ class InferWorker(QObject):
     # R pixels (contact edges, touching cells, nearest neighbour; contact_table gives the pairs; whole pixels, nothing beyond
     # R; inference/cells.py)
     neighbors = None
+    # [extension] cell_table: None = off; THR, a whole number of grey levels in 1 .. 65535: the table ends with every cell's
+    # fluorescent foci per measured channel (local maxima of an exact band-pass response of at least THR; spot_table gives the
+    # spots; whole pixels, a fixed threshold; inference/cells.py); spot_scale: 1 .. 5, the size of the foci
+    spots = None
+    spot_scale = 2
     # [extension] test-time augmentation (inference/tta.py): 1 = off (no existing route changes), 2 / 4 / 8 =
     # every frame is predicted under that many flips / rotations, the predictions are mapped back and averaged (fp32, in
     # member order) and the average is segmented: K network forwards per frame.  Whole-frame inference only
@@ -889,15 +894,29 @@ class InferWorker(QObject):
         (numbers of the source image, they name the columns) are measured.  Overlap linking: no motion model, no gap
         closing; with ``self.drift`` set, under the estimated stage drift of every frame pair; with ``self.hull`` set, with
         the outline columns; with ``self.midline`` set, with the midline columns; with ``self.percentiles`` set, with the
-        percentile columns; with ``self.neighbors`` set, with the neighbourhood columns. """
+        percentile columns; with ``self.neighbors`` set, with the neighbourhood columns; with ``self.spots`` set, with the
+        spot columns at ``self.spot_scale``. """
         from .cells import measure_cells
         df = measure_cells(results, img, link=True, min_overlap=self.min_overlap, device=self.device, drift=self.drift,
-                           hull=self.hull, midline=self.midline, percentiles=self.percentiles, neighbors=self.neighbors)
+                           hull=self.hull, midline=self.midline, percentiles=self.percentiles, neighbors=self.neighbors,
+                           spots=self.spots, spot_scale=self.spot_scale)
         if img is not None and channels is not None:      # the view holds the chosen channels only: name them by source
             names = {f'{k}_ch{i}': f'{k}_ch{int(c)}' for i, c in reversed(list(enumerate(channels)))
                      for k in ('mean', 'std', 'min', 'max', 'sum', 'bg_mean') +
-                     tuple(f'{b}p{int(q)}' for q in (self.percentiles or ()) for b in ('', 'bg_'))}
+                     tuple(f'{b}p{int(q)}' for q in (self.percentiles or ()) for b in ('', 'bg_')) +
+                     (('n_spots', 'spot_max', 'spot_sum', 'bg_spots') if self.spots is not None else ())}
             df = df.rename(columns=names)
+        return df
+
+    def spot_table(self, results, img, channels=None):
+        """ [extension] The fluorescent foci of a segmented stack (inference/cells.py ``cell_spots``): one row per spot of at
+        least ``self.spots`` grey levels at ``self.spot_scale``, with the cell it lies on and its position along the cell's
+        axes.  ``img`` as for ``cell_table``; ``channels``: the numbers of the source image the view's channels have (they
+        go into the ``channel`` column).  Whole pixels, a fixed threshold; spots on the background are left out. """
+        from .cells import cell_spots
+        df = cell_spots(results, img, spots=self.spots, spot_scale=self.spot_scale, device=self.device)
+        if channels is not None:
+            df['channel'] = df['channel'].map(lambda i: int(channels[i]))
         return df
 
     def contact_table(self, results):
