@@ -26,7 +26,13 @@ def lib():
 
 
 def _f32(a):
-    return np.ascontiguousarray(np.squeeze(a), dtype=np.float32)
+    """(H, W, 1) -> (H, W): only the trailing axis goes, so frames of one row or one column keep their two axes"""
+    a = np.asarray(a)
+    if a.ndim == 3 and a.shape[2] == 1:
+        a = a[..., 0]
+    elif a.ndim != 2:
+        a = np.squeeze(a)
+    return np.ascontiguousarray(a, dtype=np.float32)
 
 
 def gaussian05(x):

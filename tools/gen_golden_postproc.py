@@ -1,7 +1,8 @@
 #!/opt/conda/bin/python3.9
 """Generate tests/golden/postproc_*.npz with the REAL reference post-processing (build container only).
 
-Run:  PYTHONDONTWRITEBYTECODE=1 /opt/conda/bin/python3.9 -W ignore tools/gen_golden_postproc.py
+Run:  PYTHONDONTWRITEBYTECODE=1 /opt/conda/bin/python3.9 -W ignore tools/gen_golden_postproc.py [geometry]
+("geometry": only postproc_geometry.npz, the structured worst-case frames of tests/geometry_ref.py)
 Imports /root/reference/src/inference/postprocessing.py (scipy 1.7.1 / scikit-image 0.18.3 of the conda env) and
 stores only inputs + the outputs the reference produced for them (plus a few third-party known answers:
 scipy gaussian_filter, skimage label / watershed on raw arrays).
@@ -81,8 +82,36 @@ def distance_case(name, cell, border, pairs):
     save(name, **out)
 
 
+def geometry():
+    """postproc_geometry.npz: the reference's answers on the deterministic patterns of tests/geometry_ref.py — tied
+    lattices, a serpentine with a seed at each end, mirror pairs, a plateau (distance method, both threshold pairs, (H, W, 1)
+    and (H, W) inputs) and a checkerboard and a serpentine through the boundary method.  Inputs are stored with the outputs,
+    so the fixture also pins the generators."""
+    root = pathlib.Path(__file__).resolve().parents[1]
+    sys.path[:0] = [str(root), str(root / "tests")]
+    import geometry_ref as G
+    out = {"th": np.array(G.THS, np.float64)}
+    for name, (cell, border, _) in G.fixture_distance_cases().items():
+        out[f"{name}/cell"], out[f"{name}/border"] = cell, border
+        for j, (th_cell, th_seed) in enumerate(G.THS):
+            lab = distance_postprocessing(border_prediction=border[..., None].copy(), cell_prediction=cell[..., None].copy(),
+                                          th_seed=th_seed, th_cell=th_cell)
+            lab2 = distance_postprocessing(border_prediction=border.copy(), cell_prediction=cell.copy(), th_seed=th_seed,
+                                           th_cell=th_cell)
+            out[f"{name}/labels_hw1_{j}"], out[f"{name}/labels_2d_{j}"] = lab, lab2
+            print("   ", name, (th_cell, th_seed), "instances", int(lab.max()))
+    for name, (probs, _) in G.fixture_boundary_cases().items():
+        out[f"{name}/probs"] = probs
+        out[f"{name}/labels"] = boundary_postprocessing(probs.copy())
+        print("   ", name, "instances", int(out[f"{name}/labels"].max()))
+    save("geometry", **out)
+
+
 def main():
     OUT.mkdir(parents=True, exist_ok=True)
+    if sys.argv[1:] == ["geometry"]:
+        return geometry()
+    geometry()
     grid = [(0.10, 0.45), (0.05, 0.35), (0.125, 0.45)]   # defaults + eval grid corners (eval.py:128)
 
     rng = np.random.Generator(np.random.PCG64(31))
