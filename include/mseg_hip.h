@@ -591,6 +591,32 @@ int mseg_cell_links_shifted(const void* labels, int dtype, int T, int H, int W, 
                             int64_t table_cap, const int32_t* shift, int32_t* pred, int32_t* overlap, int32_t* status,
                             void* ws, size_t ws_bytes, void* stream);
 
+/* ---- linking under a tile-wise displacement field (csrc/drift.hip, csrc/cells.hip) — an extension ---------
+ * labels, dtype, label_off and the foreground F_t as above.  tile = B, one of 64, 128, 256; frame t is cut into
+ * ty = ceil(H / B) x tx = ceil(W / B) tiles, tile (j, i) = rows jB .. min((j + 1)B, H) - 1, columns iB .. min((i + 1)B, W) - 1.
+ * mseg_stack_flow: r = radius, 0 <= r <= 32; base: int32 [T][2] = (by_t, bx_t) on the device, entry 0 unused, the shift of
+ *   the pair (t - 1, t) around which its tiles search; any int32 is legal.  scores: uint32 [T - 1][ty][tx][2r + 1][2r + 1]
+ *   on the device, written whole by the call:
+ *     scores[t - 1][j][i][ey + r][ex + r] = #{(y, x) in tile (j, i) of frame t: 0 <= y - by_t - ey < H,
+ *                                              0 <= x - bx_t - ex < W, F_t(y, x) and F_{t-1}(y - by_t - ey, x - bx_t - ex)}
+ *   The source is read from the whole of frame t - 1, not from the tile: cells that enter a tile from a neighbouring tile
+ *   count; a source outside the frame counts nothing.  Summed over the tiles this is mseg_stack_drift's score at the shift
+ *   base + e.  T == 1 writes nothing.  Every score is one plain store: identical bytes from run to run.
+ *   H * W < 2^31 - 512.  ws >= mseg_stack_flow_workspace_bytes (= mseg_stack_drift_workspace_bytes; 0 = bad arguments);
+ *   MSEG_EINVAL: bad arguments, a tile not listed, r outside 0 .. 32, a dtype not listed; MSEG_EWORKSPACE: ws_bytes too
+ *   small; either way nothing is written.
+ * mseg_cell_links_field: mseg_cell_links (same outputs, workspace, pair table, status word, redo rule and tie rule) with
+ *   another pairing: pixel (y, x) of frame t pairs with (y - field[t][y / B][x / B][0], x - field[t][y / B][x / B][1]) of
+ *   frame t - 1, or with nothing where that lies outside the frame.  field: int32 [T][ty][tx][2] on the device, frame 0
+ *   unused; any int32 is legal.  A field constant over every frame: the outputs of mseg_cell_links_shifted with that shift,
+ *   byte for byte.  MSEG_EINVAL also for a tile not listed.                                                               */
+size_t mseg_stack_flow_workspace_bytes(int T, int H, int W);
+int mseg_stack_flow(const void* labels, int dtype, int T, int H, int W, const int64_t* label_off, int tile, int radius,
+                    const int32_t* base, uint32_t* scores, void* ws, size_t ws_bytes, void* stream);
+int mseg_cell_links_field(const void* labels, int dtype, int T, int H, int W, const int64_t* label_off, int64_t n_labels,
+                          int64_t table_cap, int tile, const int32_t* field, int32_t* pred, int32_t* overlap,
+                          int32_t* status, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- per-cell outline measures (csrc/hull.hip) — an extension --------------------------------------------
  * labels, dtype and label_off as for mseg_cell_links.  A cell is the union of the closed unit squares of its pixels: pixel
  * (y, x) is the square with the corners (y, x) .. (y + 1, x + 1), so corners are integer points in 0..H x 0..W.  A cell may

@@ -11,6 +11,7 @@ the GUI's Export button (inference/result_export.py) for the segmented channel o
 ``--tta K`` segments the average of the predictions of K flipped / rotated copies of every frame (inference/tta.py);
 ``--scale S`` predicts every frame at S times its resolution and segments at its own (inference/resample.py);
 ``--drift [R]`` with ``--cells``: cells are linked under the stage drift found within +-R pixels (inference/cells.py);
+``--flow [r] [--flow_tile B]`` with ``--cells --drift``: cells are linked under one shift per B px tile, within +-r pixels of the drift;
 ``--hull`` with ``--cells``: perimeter, convex hull and Feret length / width / angle of every cell (inference/cells.py);
 ``--midline`` with ``--cells``: the thinned midline of every cell: its length, for bent and filamentous cells (inference/cells.py);
 ``--percentiles [P ...]`` with ``--cells``: percentiles (default 50, the median) of every cell's pixel values and of the background;
@@ -82,6 +83,13 @@ class Parser(argparse.ArgumentParser):
 
     def parse_args(self, args=None, namespace=None):
         ns = super().parse_args(args, namespace)
+        if ns.flow is not None:
+            if not ns.cells:
+                self.error('--flow needs --cells (it changes how the cell table links frames)')
+            if ns.drift is None:
+                self.error('--flow needs --drift (the tiles search around the stage drift of every frame pair)')
+            if not 0 <= ns.flow <= 32:
+                self.error(f'--flow: a search radius of 0 .. 32 pixels expected, got {ns.flow}')
         if ns.drift is not None:
             if not ns.cells:
                 self.error('--drift needs --cells (it changes how the cell table links frames)')
@@ -187,6 +195,16 @@ def build_parser():
                              'masks overlap most is found on the device, cells are linked under it, and the table gains '
                              'drift_y / drift_x (the shift against frame 0) and centroid_y_reg / centroid_x_reg.  '
                              'Translation in whole pixels only: no rotation, no scaling, no registered image stack')
+    parser.add_argument('--flow', nargs='?', const=8, default=None, type=int, metavar='r',
+                        help='[extension] with --cells --drift: link under a tile-wise displacement field, for cells that '
+                             'move against each other (a colony expanding from its centre).  Every tile of a frame gets the '
+                             'whole-pixel shift within +-r pixels of the pair\'s stage drift (default r = 8, 0 <= r <= 32) '
+                             'under which it overlaps the previous mask most, found on the device; cells are linked under '
+                             'that field, and the table gains flow_y / flow_x (the shift of the cell\'s tile against the '
+                             'previous frame, drift included).  One shift per tile: no smoothing or interpolation of the '
+                             'field, no rotation, no per-cell search, no gap closing')
+    parser.add_argument('--flow_tile', default=64, type=int, choices=[64, 128, 256],
+                        help='[extension] with --flow: the tile edge in pixels (default 64)')
     parser.add_argument('--hull', default=False, action='store_true',
                         help='[extension] with --cells: add the measures of every cell\'s pixel outline: perimeter (exposed '
                              'pixel edges), convex_area and solidity, feret_max / feret_min (largest and smallest caliper: '
@@ -267,6 +285,8 @@ def main():
     worker.apply_clahe = args.clahe
     worker.min_overlap = args.min_overlap
     worker.drift = args.drift
+    worker.flow = args.flow
+    worker.flow_tile = args.flow_tile
     worker.hull = args.hull
     worker.midline = args.midline
     worker.percentiles = tuple(args.percentiles) if args.percentiles else None
@@ -277,6 +297,9 @@ def main():
     worker.scale = args.scale
     if args.drift is not None:
         print(f'Cell table: linking under the stage drift found within +-{args.drift} px per frame pair')
+    if args.flow is not None:
+        print(f'Cell table: linking under a displacement field of {args.flow_tile} px tiles, each searched within '
+              f'+-{args.flow} px of the stage drift')
     if args.hull:
         print('Cell table: with the outline measures (perimeter, convex hull, Feret length / width / angle)')
     if args.midline:

@@ -6,6 +6,7 @@
 //                      cell and channel sum / sum of squares / min / max; the same per frame over the background
 //   mseg_cell_links    per cell of frame t the label of frame t - 1 that shares the most pixels with it
 //   mseg_cell_links_shifted  the same with frame t - 1 moved by a per-pair integer shift (drift compensation, §6o)
+//   mseg_cell_links_field    the same with one integer shift per tile of frame t (tile-wise displacement field, §6v)
 // Everything is integer arithmetic with order-free 64-bit atomics: bit-identical from run to run.
 #include "common.h"
 
@@ -355,10 +356,12 @@ __global__ void __launch_bounds__(CM_BLOCK) cl_pairs_kernel(const L* __restrict_
 // The pairs under a per-pair shift: pixel (y, x) of frame t pairs with (y - dy_t, x - dx_t) of frame t - 1.  A lane folds 8
 // consecutive pixels of ONE row of frame t (the shifted source is contiguous within a row only, so a run never crosses a
 // row end); the frame t - 1 pixels are in general unaligned and partly outside the frame: scalar loads under a bounds test.
-template <typename L>
+// FIELD: shift is [T][ty][tx][2], one (dy, dx) per tile x tile pixels of frame t (§6v); a lane's 8 pixels start at a multiple
+// of 8 and the tile is one, so they lie in one tile: the same kernel with a per-lane lookup.
+template <typename L, bool FIELD>
 __global__ void __launch_bounds__(CM_BLOCK) cl_pairs_shifted_kernel(const L* __restrict__ lab, int T, int H, int W,
                                                                     const int64_t* __restrict__ loff,
-                                                                    const int32_t* __restrict__ shift,
+                                                                    const int32_t* __restrict__ shift, int tile,
                                                                     u64* __restrict__ keys, uint32_t* __restrict__ cnt,
                                                                     uint32_t cap, int32_t* __restrict__ status) {
   const int64_t per_row = ((int64_t)W + CM_PPL - 1) / CM_PPL, groups = (int64_t)H * per_row;
@@ -368,7 +371,9 @@ __global__ void __launch_bounds__(CM_BLOCK) cl_pairs_shifted_kernel(const L* __r
   const int64_t in_frame = g - (int64_t)(t - 1) * groups;
   const int y = (int)(in_frame / per_row);
   const int x0 = (int)(in_frame - (int64_t)y * per_row) * CM_PPL;
-  const int64_t ys = (int64_t)y - shift[2 * t], xs0 = (int64_t)x0 - shift[2 * t + 1];
+  int64_t at = t;
+  if (FIELD) at = ((int64_t)t * ((H + tile - 1) / tile) + y / tile) * ((W + tile - 1) / tile) + x0 / tile;
+  const int64_t ys = (int64_t)y - shift[2 * at], xs0 = (int64_t)x0 - shift[2 * at + 1];
   if (ys < 0 || ys >= H || xs0 + CM_PPL <= 0 || xs0 >= W) return;      // no pixel of this lane has a source
   const int nvalid = min(CM_PPL, W - x0);
   const int64_t Kl = loff[t + 1] - loff[t], Km = loff[t] - loff[t - 1];
@@ -520,9 +525,10 @@ extern "C" int mseg_cell_links(const void* labels, int dtype, int T, int H, int 
   return MSEG_OK;
 }
 
-extern "C" int mseg_cell_links_shifted(const void* labels, int dtype, int T, int H, int W, const int64_t* label_off,
-                                       int64_t n_labels, int64_t table_cap, const int32_t* shift, int32_t* pred,
-                                       int32_t* overlap, int32_t* status, void* ws, size_t ws_bytes, void* stream) {
+// mseg_cell_links_shifted (tile == 0: shift is [T][2]) and mseg_cell_links_field (shift is [T][ty][tx][2])
+static int cl_links_moved(const void* labels, int dtype, int T, int H, int W, const int64_t* label_off, int64_t n_labels,
+                          int64_t table_cap, const int32_t* shift, int tile, int32_t* pred, int32_t* overlap,
+                          int32_t* status, void* ws, size_t ws_bytes, void* stream) {
   if (!labels || !label_off || !shift || !status || !ws || T <= 0 || H <= 0 || W <= 0 || n_labels < 0) return MSEG_EINVAL;
   if ((int64_t)H * W >= (1ll << 31) - CM_PPL) return MSEG_EINVAL;
   if (dtype != MSEG_PIX_U16 && dtype != MSEG_PIX_I32) return MSEG_EINVAL;
@@ -542,12 +548,15 @@ extern "C" int mseg_cell_links_shifted(const void* labels, int dtype, int T, int
   if (hipMemsetAsync(ws, 0, need, st) != hipSuccess) return MSEG_ELAUNCH;
   if (T > 1) {
     const int64_t lanes = (int64_t)(T - 1) * H * (((int64_t)W + CM_PPL - 1) / CM_PPL);
-    if (dtype == MSEG_PIX_U16)
-      hipLaunchKernelGGL(cl_pairs_shifted_kernel<uint16_t>, dim3(cl_blocks(lanes)), dim3(CM_BLOCK), 0, st,
-                         (const uint16_t*)labels, T, H, W, label_off, shift, keys, cnt, cap, status);
-    else
-      hipLaunchKernelGGL(cl_pairs_shifted_kernel<int32_t>, dim3(cl_blocks(lanes)), dim3(CM_BLOCK), 0, st,
-                         (const int32_t*)labels, T, H, W, label_off, shift, keys, cnt, cap, status);
+#define CL_GO(L, FIELD)                                                                                                \
+  hipLaunchKernelGGL((cl_pairs_shifted_kernel<L, FIELD>), dim3(cl_blocks(lanes)), dim3(CM_BLOCK), 0, st, (const L*)labels, T, \
+                     H, W, label_off, shift, tile, keys, cnt, cap, status)
+    if (dtype == MSEG_PIX_U16) {
+      if (tile) CL_GO(uint16_t, true); else CL_GO(uint16_t, false);
+    } else {
+      if (tile) CL_GO(int32_t, true); else CL_GO(int32_t, false);
+    }
+#undef CL_GO
     const int64_t entries = (int64_t)(T - 1) * cap;
     hipLaunchKernelGGL(cl_best_kernel, dim3(cl_blocks(entries)), dim3(CM_BLOCK), 0, st, (const u64*)keys,
                        (const uint32_t*)cnt, entries, cap, label_off, best);
@@ -556,4 +565,19 @@ extern "C" int mseg_cell_links_shifted(const void* labels, int dtype, int T, int
                      overlap);
   MSEG_LAUNCH_CHECK();
   return MSEG_OK;
+}
+
+extern "C" int mseg_cell_links_shifted(const void* labels, int dtype, int T, int H, int W, const int64_t* label_off,
+                                       int64_t n_labels, int64_t table_cap, const int32_t* shift, int32_t* pred,
+                                       int32_t* overlap, int32_t* status, void* ws, size_t ws_bytes, void* stream) {
+  return cl_links_moved(labels, dtype, T, H, W, label_off, n_labels, table_cap, shift, 0, pred, overlap, status, ws, ws_bytes,
+                        stream);
+}
+
+extern "C" int mseg_cell_links_field(const void* labels, int dtype, int T, int H, int W, const int64_t* label_off,
+                                     int64_t n_labels, int64_t table_cap, int tile, const int32_t* field, int32_t* pred,
+                                     int32_t* overlap, int32_t* status, void* ws, size_t ws_bytes, void* stream) {
+  if (tile != 64 && tile != 128 && tile != 256) return MSEG_EINVAL;
+  return cl_links_moved(labels, dtype, T, H, W, label_off, n_labels, table_cap, field, tile, pred, overlap, status, ws,
+                        ws_bytes, stream);
 }

@@ -3,9 +3,11 @@
 //   mseg_stack_drift   labels [T][H][W] -> scores uint32 [T - 1][2R + 1][2R + 1]: for every frame pair (t - 1, t) and every
 //                      integer shift (dy, dx), |dy|, |dx| <= R, the number of pixels where the foreground of frame t - 1
 //                      moved by (dy, dx) lies on the foreground of frame t
-// Two kernels: the labels are packed into one foreground bit per pixel once (dr_pack_kernel), the scores are popcounts of
-// ANDed 64-bit words of those bit rows (dr_score_kernel), 64 pixels per operation.  Integer atomics only: bit-identical
-// from run to run.
+//   mseg_stack_flow    the same count per tile of frame t (64 / 128 / 256 px) and per deviation (ey, ex), |ey|, |ex| <= r <= 32,
+//                      from a per-pair base shift: the score surfaces of a tile-wise displacement field
+// Two kernels each: the labels are packed into one foreground bit per pixel once (dr_pack_kernel), the scores are popcounts of
+// ANDed 64-bit words of those bit rows (dr_score_kernel; per tile from LDS: fl_score_kernel), 64 pixels per operation.
+// Integer atomics (dr_score_kernel) or one plain store per score (fl_score_kernel): bit-identical from run to run.
 #include "common.h"
 
 #define DR_BLOCK 256
@@ -18,6 +20,7 @@
 #define DR_MIN_ROWS 8             // rows of one thread at least (one atomic per thread)
 #define DR_TARGET_THREADS (1 << 21)   // 256 compute units x 2048 resident lanes x 4: enough waves to hide the L1 / L2 loads
 #define DR_MAX_GRID (1 << 20)
+#define FL_MAX_R 32               // below 64: a tile row's window is the tile's words and ONE word on either side
 
 namespace {
 
@@ -89,6 +92,88 @@ __global__ void __launch_bounds__(DR_BLOCK) dr_score_kernel(const u64* __restric
   }
 }
 
+// Two frames of one tile and the deviations around it.  A workgroup owns one (pair, tile) and keeps in LDS
+//   cur  the tile's B rows x B / 64 words of frame t (zero rows below the frame), and
+//   win  B + 2r rows x B / 64 + 2 words of frame t - 1 MOVED BY THE PAIR'S BASE SHIFT: window word (wy, k) holds the moved
+//        frame's row jB - r + wy, columns iB - 64 + 64k .. + 63.  It is bounds-tested and funnel-shifted while it is filled,
+//        with zeros outside the frame: the one place that sees |bx| >= 64, negative shifts and sources outside the frame.
+// A thread then owns whole deviations (ey, ex), ex fastest, and walks the tile's rows as dr_score_kernel does; with |ex| <=
+// 32 the moved word under tile word w starts in window word w or w + 1.  Every (tile, deviation) has one owner: a plain
+// store, no atomics, no memset.
+template <int NWT>                // words of a tile row
+__global__ void __launch_bounds__(DR_BLOCK) fl_score_kernel(const u64* __restrict__ bits, int T, int H, int W, int r,
+                                                            const int32_t* __restrict__ base, int ty, int tx,
+                                                            uint32_t* __restrict__ scores) {
+  extern __shared__ __align__(16) u64 fl_lds[];
+  constexpr int B = 64 * NWT, NWW = NWT + 2;
+  u64* cur = fl_lds;
+  u64* win = fl_lds + B * NWT;
+  const int S = 2 * r + 1;
+  const int nw = (W + 63) / 64;
+  const int64_t stride = (int64_t)nw + DR_PAD_L + DR_PAD_R;
+  const int64_t total = (int64_t)(T - 1) * ty * tx;
+  for (int64_t wg = blockIdx.x; wg < total; wg += gridDim.x) {      // wg = (pair * ty + j) * tx + i
+    const int i = (int)(wg % tx), j = (int)(wg / tx % ty), pair = (int)(wg / tx / ty);
+    const int64_t by = base[2 * (pair + 1)], bx = base[2 * (pair + 1) + 1];
+    const u64* __restrict__ ft = bits + (int64_t)(pair + 1) * H * stride + DR_PAD_L;
+    const u64* __restrict__ fp = bits + (int64_t)pair * H * stride + DR_PAD_L;
+    for (int k = threadIdx.x; k < B * NWT; k += blockDim.x) {
+      const int ry = k / NWT, iw = i * NWT + (k - ry * NWT);
+      const int y = j * B + ry;
+      cur[k] = (y < H && iw < nw) ? ft[(int64_t)y * stride + iw] : 0;
+    }
+    for (int k = threadIdx.x; k < (B + 2 * r) * NWW; k += blockDim.x) {
+      const int wy = k / NWW, kw = k - wy * NWW;
+      const int64_t ys = (int64_t)j * B - r + wy - by;              // the source row and the source column of bit 0
+      const int64_t p = (int64_t)i * B - 64 + 64 * kw - bx;
+      const int64_t q = p >> 6;                                     // floor
+      const int s = (int)(p & 63);
+      u64 v = 0;
+      if (ys >= 0 && ys < H) {
+        const u64* __restrict__ row = fp + ys * stride;
+        const u64 lo = (q >= 0 && q < nw) ? row[q] : 0;
+        const u64 hi = (q + 1 >= 0 && q + 1 < nw) ? row[q + 1] : 0;
+        v = s ? (lo >> s) | (hi << (64 - s)) : lo;
+      }
+      win[k] = v;
+    }
+    __syncthreads();
+    const int rows = min(B, H - j * B);                             // the rows below are zero in cur
+    for (int e = threadIdx.x; e < S * S; e += blockDim.x) {
+      const int eyi = e / S, exi = e - eyi * S;
+      const int off = 64 - (exi - r);                               // 32 .. 96: window bit under bit 0 of tile word 0
+      const int s = off & 63;
+      const u64* a = win + (2 * r - eyi) * NWW + (off >> 6);        // tile row ry lies under window row ry - ey + r
+      uint32_t acc = 0;
+      for (int ry = 0; ry < rows; ++ry) {
+        u64 lo = a[ry * NWW];
+#pragma unroll
+        for (int w = 0; w < NWT; ++w) {
+          const u64 hi = a[ry * NWW + w + 1];
+          const u64 moved = s ? (lo >> s) | (hi << (64 - s)) : lo;
+          acc += (uint32_t)__popcll(cur[ry * NWT + w] & moved);
+          lo = hi;
+        }
+      }
+      scores[(wg * S + eyi) * S + exi] = acc;
+    }
+    __syncthreads();
+  }
+}
+
+// labels -> bits [T][H][stride] on the stream
+void dr_pack(const void* labels, int dtype, int T, int H, int W, const int64_t* label_off, u64* bits, hipStream_t st) {
+  const int64_t words = (int64_t)T * H * dr_row_stride(W);
+  int64_t grid = (words + DR_WAVES - 1) / DR_WAVES;
+  if (grid > DR_MAX_GRID) grid = DR_MAX_GRID;
+  if (dtype == MSEG_PIX_U16)
+    hipLaunchKernelGGL(dr_pack_kernel<uint16_t>, dim3((unsigned)grid), dim3(DR_BLOCK), 0, st, (const uint16_t*)labels, T, H,
+                       W, label_off, bits);
+  else
+    hipLaunchKernelGGL(dr_pack_kernel<int32_t>, dim3((unsigned)grid), dim3(DR_BLOCK), 0, st, (const int32_t*)labels, T, H, W,
+                       label_off, bits);
+}
+
 }  // namespace
 
 extern "C" size_t mseg_stack_drift_workspace_bytes(int T, int H, int W) {
@@ -110,15 +195,7 @@ extern "C" int mseg_stack_drift(const void* labels, int dtype, int T, int H, int
   const int64_t cells = (int64_t)(T - 1) * S * S;
   if (hipMemsetAsync(scores, 0, sizeof(uint32_t) * (size_t)cells, st) != hipSuccess) return MSEG_ELAUNCH;
   u64* bits = (u64*)ws;
-  const int64_t words = (int64_t)T * H * dr_row_stride(W);
-  int64_t grid = (words + DR_WAVES - 1) / DR_WAVES;
-  if (grid > DR_MAX_GRID) grid = DR_MAX_GRID;
-  if (dtype == MSEG_PIX_U16)
-    hipLaunchKernelGGL(dr_pack_kernel<uint16_t>, dim3((unsigned)grid), dim3(DR_BLOCK), 0, st, (const uint16_t*)labels, T, H,
-                       W, label_off, bits);
-  else
-    hipLaunchKernelGGL(dr_pack_kernel<int32_t>, dim3((unsigned)grid), dim3(DR_BLOCK), 0, st, (const int32_t*)labels, T, H, W,
-                       label_off, bits);
+  dr_pack(labels, dtype, T, H, W, label_off, bits, st);
   // row chunks: as many as it takes to reach DR_TARGET_THREADS threads, of at least DR_MIN_ROWS rows each
   int64_t chunks = (DR_TARGET_THREADS + cells - 1) / cells;
   const int64_t most = ((int64_t)H + DR_MIN_ROWS - 1) / DR_MIN_ROWS;
@@ -126,10 +203,46 @@ extern "C" int mseg_stack_drift(const void* labels, int dtype, int T, int H, int
   if (chunks < 1) chunks = 1;
   const int rows = (int)(((int64_t)H + chunks - 1) / chunks);
   chunks = ((int64_t)H + rows - 1) / rows;
-  grid = (cells * chunks + DR_BLOCK - 1) / DR_BLOCK;
+  int64_t grid = (cells * chunks + DR_BLOCK - 1) / DR_BLOCK;
   if (grid > DR_MAX_GRID) grid = DR_MAX_GRID;
   hipLaunchKernelGGL(dr_score_kernel, dim3((unsigned)grid), dim3(DR_BLOCK), 0, st, (const u64*)bits, T, H, W, max_drift, rows,
                      (int)chunks, scores);
+  MSEG_LAUNCH_CHECK();
+  return MSEG_OK;
+}
+
+extern "C" size_t mseg_stack_flow_workspace_bytes(int T, int H, int W) { return mseg_stack_drift_workspace_bytes(T, H, W); }
+
+extern "C" int mseg_stack_flow(const void* labels, int dtype, int T, int H, int W, const int64_t* label_off, int tile,
+                               int radius, const int32_t* base, uint32_t* scores, void* ws, size_t ws_bytes, void* stream) {
+  if (!labels || !label_off || !base || !ws || T <= 0 || H <= 0 || W <= 0) return MSEG_EINVAL;
+  if ((int64_t)H * W >= (1ll << 31) - 512) return MSEG_EINVAL;
+  if (dtype != MSEG_PIX_U16 && dtype != MSEG_PIX_I32) return MSEG_EINVAL;
+  if (tile != 64 && tile != 128 && tile != 256) return MSEG_EINVAL;
+  if (radius < 0 || radius > FL_MAX_R) return MSEG_EINVAL;
+  if (T > 1 && !scores) return MSEG_EINVAL;
+  if (ws_bytes < mseg_stack_flow_workspace_bytes(T, H, W)) return MSEG_EWORKSPACE;
+  if (T == 1) return MSEG_OK;
+  hipStream_t st = (hipStream_t)stream;
+  u64* bits = (u64*)ws;
+  dr_pack(labels, dtype, T, H, W, label_off, bits, st);
+  const int ty = (H + tile - 1) / tile, tx = (W + tile - 1) / tile, nwt = tile / 64;
+  const int S2 = (2 * radius + 1) * (2 * radius + 1);
+  // a thread owns whole deviations: the largest workgroup whose lanes' turns are at least 90 % used (r = 8: 289 deviations
+  // are 5 turns of 64 lanes, but 2 of 256 with the second nearly empty), else one wave
+  int block = 64;
+  for (int b = DR_BLOCK; b > 64; b /= 2)
+    if (10 * S2 >= 9 * ((S2 + b - 1) / b * b)) { block = b; break; }
+  int64_t grid = (int64_t)(T - 1) * ty * tx;
+  if (grid > DR_MAX_GRID) grid = DR_MAX_GRID;
+  const size_t lds = sizeof(u64) * ((size_t)tile * nwt + (size_t)(tile + 2 * radius) * (nwt + 2));
+#define FL_GO(N)                                                                                                          \
+  hipLaunchKernelGGL(fl_score_kernel<N>, dim3((unsigned)grid), dim3(block), lds, st, (const u64*)bits, T, H, W, radius, base, \
+                     ty, tx, scores)
+  if (nwt == 1) FL_GO(1);
+  else if (nwt == 2) FL_GO(2);
+  else FL_GO(4);
+#undef FL_GO
   MSEG_LAUNCH_CHECK();
   return MSEG_OK;
 }

@@ -9,7 +9,11 @@ previous frame it shares the most pixels with.  There is no motion model and no 
 than its own extent between two frames, or that is missed in one frame, starts a new track.  ``drift=R`` takes the
 usual cause of such jumps out first: the whole field of view moving by a few (tens of) pixels between time points.  The
 integer shift of every frame pair is the peak of the device's foreground-overlap surface (csrc/drift.hip:
-``mseg_stack_drift``), and the links are taken under it (``mseg_cell_links_shifted``).  ``hull=True`` adds
+``mseg_stack_drift``), and the links are taken under it (``mseg_cell_links_shifted``).  ``flow=r`` goes on
+from there for stacks whose cells move AGAINST EACH OTHER, as in a growing colony: every tile of every frame gets its own
+whole-pixel shift, the peak of the tile's overlap surface within +-r pixels of the pair's drift (``mseg_stack_flow``;
+DESIGN.md §6v), and the links are taken under that field (``mseg_cell_links_field``).  No sub-pixel or smoothed field, no
+rotation, no per-cell search, still no gap closing.  ``hull=True`` adds
 the measures of the cell's PIXEL OUTLINE people take from rod-shaped microbes: crack perimeter, convex hull, largest and
 smallest caliper (csrc/hull.hip: ``mseg_cell_hull``).  No sub-pixel contour is fitted.  ``midline=True`` adds the
 length along a BENT cell, where the largest caliper is only the chord: every cell is thinned alone to a one-pixel skeleton
@@ -46,6 +50,7 @@ SHAPE_COLUMNS = ['frame', 'label', 'area', 'centroid_y', 'centroid_x', 'bbox_min
 CHANNEL_COLUMNS = ['mean_ch{c}', 'std_ch{c}', 'min_ch{c}', 'max_ch{c}', 'sum_ch{c}', 'bg_mean_ch{c}']
 LINK_COLUMNS = ['pred_label', 'overlap', 'track_id', 'parent_track']
 DRIFT_COLUMNS = ['drift_y', 'drift_x', 'centroid_y_reg', 'centroid_x_reg']
+FLOW_COLUMNS = ['flow_y', 'flow_x']
 HULL_COLUMNS = ['perimeter', 'convex_area', 'solidity', 'feret_max', 'feret_min', 'feret_angle', 'feret_y0', 'feret_x0',
                 'feret_y1', 'feret_x1']
 MIDLINE_COLUMNS = ['skeleton_pixels', 'skeleton_length', 'skeleton_ends', 'skeleton_branches', 'midline_length',
@@ -53,6 +58,8 @@ MIDLINE_COLUMNS = ['skeleton_pixels', 'skeleton_length', 'skeleton_ends', 'skele
 PERCENTILE_COLUMNS = ['p{p}_ch{c}', 'bg_p{p}_ch{c}']     # all cell columns (channel by channel), then all background columns
 MAX_PERCENTILES = 8   # 2 ranks each: the 16 ranks mseg_cell_order_stats accepts
 MAX_DRIFT = 128       # largest search radius mseg_stack_drift accepts
+MAX_FLOW = 32         # largest search radius mseg_stack_flow accepts
+FLOW_TILES = (64, 128, 256)    # the tile sizes mseg_stack_flow and mseg_cell_links_field accept
 NEIGHBOR_COLUMNS = ['contact_length', 'border_length', 'contact_fraction', 'n_touching', 'n_neighbors', 'nn_label',
                     'nn_distance', 'nn_gap', 'contact_label', 'contact_max']
 CONTACT_COLUMNS = ['frame', 'label_a', 'label_b', 'contact', 'distance']
@@ -66,18 +73,23 @@ SPOT_RECORD = np.dtype([('frame', '<i4'), ('channel', '<i4'), ('y', '<i4'), ('x'
                         ('d', '<i8')])      # MsegSpot
 
 
-def columns(channels=(), link=True, drift=False, hull=False, midline=False, percentiles=(), neighbors=False, spots=False):
+def columns(channels=(), link=True, drift=False, hull=False, midline=False, percentiles=(), neighbors=False, spots=False,
+            flow=False):
     """the table's columns, in order, for the measured ``channels``; ``drift``: with the drift columns (needs ``link``);
+    ``flow``: with flow_y / flow_x after the drift columns (needs ``drift``);
     ``hull``: with the outline columns; ``midline``: with the midline columns; ``percentiles``: with p{P}_ch{c} for every
     measured channel (per channel the percentiles in the order given), then bg_p{P}_ch{c} likewise; ``neighbors``: with the
     neighbourhood columns; ``spots``: with the four spot columns of every measured channel, channel by channel; these come
     last"""
     if drift and not link:
         raise ValueError("the drift columns belong to the link columns: drift needs link")
+    if flow and not drift:
+        raise ValueError("the flow columns follow the drift columns: flow needs drift")
     cols = list(SHAPE_COLUMNS)
     for c in channels:
         cols += [name.format(c=int(c)) for name in CHANNEL_COLUMNS]
     return cols + (list(LINK_COLUMNS) if link else []) + (list(DRIFT_COLUMNS) if drift else []) + \
+        (list(FLOW_COLUMNS) if flow else []) + \
         (list(HULL_COLUMNS) if hull else []) + (list(MIDLINE_COLUMNS) if midline else []) + \
         [name.format(p=int(q), c=int(c)) for name in (PERCENTILE_COLUMNS if percentiles else ()) for c in channels
          for q in percentiles] + (list(NEIGHBOR_COLUMNS) if neighbors else []) + \
@@ -434,7 +446,69 @@ def pick_drift(scores):
     return shift
 
 
-def _links_call(lab, pix, off, cap, shift=None):
+def check_flow(flow, tile=64):
+    """the rule of ``measure_cells(flow=..., flow_tile=...)``, ``InferWorker.flow`` / ``flow_tile`` and --flow / --flow_tile:
+    None, or an int in 0 .. MAX_FLOW, and a tile of FLOW_TILES -> (flow, tile)"""
+    if isinstance(tile, bool) or int(tile) != tile or int(tile) not in FLOW_TILES:
+        raise ValueError(f"flow_tile: one of {', '.join(str(b) for b in FLOW_TILES)} pixels expected, got {tile!r}")
+    if flow is None:
+        return None, int(tile)
+    if isinstance(flow, bool) or int(flow) != flow or not 0 <= int(flow) <= MAX_FLOW:
+        raise ValueError(f"flow: None or a whole number of pixels in 0 .. {MAX_FLOW} expected, got {flow!r}")
+    return int(flow), int(tile)
+
+
+def flow_raw(lab, pix, off, base, radius, tile):
+    """``mseg_stack_flow`` for the whole stack -> scores uint32 [T - 1, ty, tx, 2r + 1, 2r + 1] on the host: scores[t - 1, j,
+    i, ey + r, ex + r] = pixels of tile (j, i) of frame t where the foreground of frame t - 1 moved by base[t] + (ey, ex)
+    lies on the foreground of frame t.  ``base``: int32 [T, 2], row 0 unused"""
+    lib = _lib.load()
+    dev = lab.device
+    T, H, W = (int(v) for v in lab.shape)
+    r, B = int(radius), int(tile)
+    base = np.ascontiguousarray(base, np.int32)
+    if base.shape != (T, 2):
+        raise ValueError(f"base: int32 [{T}, 2] expected, got {base.shape}")
+    ty, tx, side = -(-H // B), -(-W // B), 2 * r + 1
+    off_d = torch.from_numpy(np.ascontiguousarray(off, np.int64)).to(dev)
+    base_d = torch.from_numpy(base).to(dev)
+    scores = torch.zeros((max(T - 1, 1), ty, tx, side, side), dtype=torch.int32, device=dev)
+    nbytes = lib.mseg_stack_flow_workspace_bytes(T, H, W)
+    if nbytes == 0:
+        raise ValueError(f"mseg_stack_flow: no workspace for a {T} x {H} x {W} stack")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    _lib.check(lib.mseg_stack_flow(lab.data_ptr(), pix, T, H, W, off_d.data_ptr(), B, r, base_d.data_ptr(),
+                                   scores.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)), "stack_flow")
+    return scores.cpu().numpy().view(np.uint32)[:T - 1]
+
+
+def pick_flow(scores, base):
+    """scores uint32 [T - 1, ty, tx, 2r + 1, 2r + 1], base int [T, 2] -> int32 [T, ty, tx, 2]: per tile base[t] + the
+    deviation (ey, ex) ``pick_drift`` picks from the tile's surface (the largest score; ties to the smallest ey^2 + ex^2,
+    then the smaller ey, then the smaller ex; (0, 0) where the best score is 0, so an empty tile falls back to the pair's
+    drift).  Frame 0 holds zeros.  Pure numpy."""
+    scores = np.asarray(scores)
+    if scores.ndim != 5 or scores.shape[3] != scores.shape[4] or scores.shape[3] % 2 == 0:
+        raise ValueError(f"scores: [T - 1, ty, tx, 2r + 1, 2r + 1] expected, got {scores.shape}")
+    pairs, ty, tx, side = scores.shape[:4]
+    base = np.asarray(base, np.int64)
+    if base.shape != (pairs + 1, 2):
+        raise ValueError(f"base: [{pairs + 1}, 2] expected, got {base.shape}")
+    d = np.arange(-(side // 2), side // 2 + 1, dtype=np.int64)
+    ey, ex = (g.ravel() for g in np.meshgrid(d, d, indexing="ij"))
+    order = np.lexsort((ex, ey, ey * ey + ex * ex))                # the deviations from the most to the least preferred
+    rank = np.empty_like(order)
+    rank[order] = np.arange(order.size)
+    # one key per (tile, deviation): the score first, then the preference; all-zero tiles end at rank 0 = (0, 0)
+    field = np.zeros((pairs + 1, ty, tx, 2), np.int32)
+    for t in range(1, pairs + 1):                                  # pair by pair: the keys of one pair at a time
+        key = scores[t - 1].reshape(ty, tx, side * side).astype(np.int64) * order.size + (order.size - 1 - rank)
+        best = key.argmax(axis=-1)
+        field[t] = base[t] + np.stack([ey[best], ex[best]], axis=-1)
+    return field
+
+
+def _links_call(lab, pix, off, cap, shift=None, tile=None):
     lib = _lib.load()
     dev = lab.device
     T, H, W = (int(v) for v in lab.shape)
@@ -447,7 +521,12 @@ def _links_call(lab, pix, off, cap, shift=None):
     if nbytes == 0:
         raise ValueError(f"mseg_cell_links: no workspace for T = {T}, {n} cells, table {cap}")
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    if shift is None:
+    if tile is not None:
+        field_d = torch.from_numpy(np.ascontiguousarray(shift, np.int32)).to(dev)
+        _lib.check(lib.mseg_cell_links_field(lab.data_ptr(), pix, T, H, W, off_d.data_ptr(), n, cap, int(tile),
+                                             field_d.data_ptr(), pred.data_ptr(), ovl.data_ptr(), status.data_ptr(),
+                                             ws.data_ptr(), ws.numel(), _stream(dev)), "cell_links_field")
+    elif shift is None:
         _lib.check(lib.mseg_cell_links(lab.data_ptr(), pix, T, H, W, off_d.data_ptr(), n, cap, pred.data_ptr(),
                                        ovl.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)),
                    "cell_links")
@@ -459,27 +538,36 @@ def _links_call(lab, pix, off, cap, shift=None):
     return pred.cpu().numpy()[:n], ovl.cpu().numpy()[:n], status.cpu().numpy()
 
 
-def link_raw(lab, pix, off, table_cap=None, shift=None):
+def link_raw(lab, pix, off, table_cap=None, shift=None, field=None, tile=None):
     """``mseg_cell_links`` for the whole stack -> (pred int32 [n], overlap int32 [n]) on the host.  The pair tables start
     at 4 entries per cell of the two frames; a frame pair whose table filled up (the device status word says so) is redone
     on its own with a table of more than H * W entries, which cannot fill up: the result is always exact.  ``shift``: int32
     [T, 2] = (dy, dx) per frame against its predecessor (row 0 unused): the links are taken under these shifts
-    (``mseg_cell_links_shifted``); None: same (y, x), as ever."""
+    (``mseg_cell_links_shifted``); None: same (y, x), as ever.  ``field`` with ``tile``: int32 [T, ty, tx, 2], one (dy, dx)
+    per ``tile`` x ``tile`` pixels of every frame (frame 0 unused): the links are taken under it (``mseg_cell_links_field``)."""
     T, H, W = (int(v) for v in lab.shape)
-    if shift is not None:
-        shift = np.ascontiguousarray(shift, np.int32)
-        if shift.shape != (T, 2):
-            raise ValueError(f"shift: int32 [{T}, 2] expected, got {shift.shape}")
+    if (field is None) != (tile is None) or (field is not None and shift is not None):
+        raise ValueError("field and tile go together, and not with shift")
+    moved = None                      # the shifts or the field: per frame, entry 0 unused
+    if field is not None:
+        moved = np.ascontiguousarray(field, np.int32)
+        if int(tile) not in FLOW_TILES or moved.shape != (T, -(-H // int(tile)), -(-W // int(tile)), 2):
+            raise ValueError(f"field: int32 [{T}, ceil({H} / tile), ceil({W} / tile), 2] with a tile of {FLOW_TILES} expected, "
+                             f"got {moved.shape} with tile {tile}")
+    elif shift is not None:
+        moved = np.ascontiguousarray(shift, np.int32)
+        if moved.shape != (T, 2):
+            raise ValueError(f"shift: int32 [{T}, 2] expected, got {moved.shape}")
     k = np.diff(off)
     if table_cap is None:
         pair = int((k[1:] + k[:-1]).max()) if T > 1 else 0
         table_cap = min(max(MIN_TABLE, _pow2(4 * pair)), _pow2(H * W + 1))
-    pred, ovl, status = _links_call(lab, pix, off, int(table_cap), shift)
+    pred, ovl, status = _links_call(lab, pix, off, int(table_cap), moved, tile)
     pred, ovl = pred.copy(), ovl.copy()
     for t in np.nonzero(status)[0]:
         sub = np.asarray(off[t - 1:t + 2], np.int64) - off[t - 1]
         p2, o2, s2 = _links_call(lab[t - 1:t + 1], pix, sub, max(MIN_TABLE, _pow2(H * W + 1)),
-                                 None if shift is None else np.stack([np.zeros(2, np.int32), shift[t]]))
+                                 None if moved is None else np.stack([np.zeros_like(moved[t]), moved[t]]), tile)
         if s2.any():
             raise RuntimeError("mseg_cell_links: a table of more than H * W entries reported full")
         pred[off[t]:off[t + 1]] = p2[sub[1]:]
@@ -857,7 +945,7 @@ def _neighborhood(v):
 
 
 def table_from_sums(off, H, W, raw, channels=(), links=None, min_overlap=1, shift=None, hull=None, midline=None,
-                    order_stats=None, neighbors=None, spots=None):
+                    order_stats=None, neighbors=None, spots=None, field=None, tile=None):
     """the DataFrame from the integer sums of ``measure_raw`` (and ``links`` = (pred, overlap) or None); host arithmetic in
     Python integers and fp64.  ``shift``: int [T, 2], the (dy, dx) of every frame against its predecessor the links were
     taken under (row 0 ignored), or None: with it the drift columns follow the link columns.  ``hull``: int [10, n], the
@@ -879,16 +967,24 @@ def table_from_sums(off, H, W, raw, channels=(), links=None, min_overlap=1, shif
     [T, C], records), the scale and the three results of ``spots_raw``, or None: with it the table ends with four columns per
     measured channel: n_spots_ch{c} = cell_count, spot_max_ch{c} = the largest D among the cell's records / 16^(2 scale) (NaN
     without a spot), spot_sum_ch{c} = the exact integer sum of their D / 16^(2 scale) (0 without), bg_spots_ch{c} = bg_count
-    of the frame"""
+    of the frame.  ``field`` with ``tile``: int [T, ty, tx, 2], the field of ``pick_flow`` the links were taken under (needs
+    ``shift``), or None: with it flow_y / flow_x follow the drift columns: the field value of the tile that holds the pixel
+    (floor(centroid_y), floor(centroid_x)), 0 in frame 0"""
     off = np.asarray(off, np.int64)
     area = raw["shape"][0]
+    if field is not None and shift is None:
+        raise ValueError("the flow columns follow the drift columns: field needs shift")
     pct = check_percentiles(order_stats[0]) if order_stats is not None else ()
     if pct and not len(channels):
         raise ValueError("percentiles are taken of an image's channels: none is measured")
     if spots is not None and not len(channels):
         raise ValueError("spots are taken of an image's channels: none is measured")
     rows = {c: [] for c in columns(channels, links is not None, shift is not None, hull is not None, midline is not None, pct,
-                                   neighbors is not None, spots is not None)}
+                                   neighbors is not None, spots is not None, field is not None)}
+    if field is not None:
+        field = np.asarray(field, np.int64).copy()
+        field[0] = 0
+        field, tile = field.tolist(), int(tile)
     if spots is not None:
         sp_unit = 1 << (8 * int(spots[0]))
         sp_n = np.asarray(spots[1]).reshape(len(channels), len(area)).tolist()
@@ -934,6 +1030,8 @@ def table_from_sums(off, H, W, raw, channels=(), links=None, min_overlap=1, shif
                 vals += [int(links[0][s]), int(links[1][s]), 0, 0]
             if shift is not None:
                 vals += [total[t][0], total[t][1], sh[1][s] / n - total[t][0], sh[2][s] / n - total[t][1]]
+            if field is not None:
+                vals += field[t][sh[1][s] // n // tile][sh[2][s] // n // tile]
             if hull is not None:
                 vals += _outline(n, [plane[s] for plane in hl])
             if midline is not None:
@@ -958,7 +1056,7 @@ def table_from_sums(off, H, W, raw, channels=(), links=None, min_overlap=1, shif
 
 
 def measure_cells(mask, img=None, channels=None, link=True, min_overlap=1, device=None, drift=None, hull=False,
-                  midline=False, percentiles=None, neighbors=None, spots=None, spot_scale=2):
+                  midline=False, percentiles=None, neighbors=None, spots=None, spot_scale=2, flow=None, flow_tile=64):
     """ One row per cell of a segmented stack, ordered by (frame, label).
 
     :param mask: label stack [T, H, W] (or one frame [H, W]): host array or device tensor (int16 holding uint16 bits, or
@@ -974,6 +1072,16 @@ def measure_cells(mask, img=None, channels=None, link=True, min_overlap=1, devic
         most pixels (``pick_drift``), the links are taken under it, and the table ends with drift_y / drift_x (the shift of
         the frame against frame 0, the same for all its rows) and centroid_y_reg / centroid_x_reg (the centroid minus that
         shift: a cell that only drifted keeps it).  Whole pixels, translation only; needs ``link``.
+    :param flow: None (default): one shift per frame pair.  r, a whole number in 0 .. 32: link under a TILE-WISE displacement
+        field, for cells that move against each other (a colony that expands from its centre).  Every ``flow_tile`` x
+        ``flow_tile`` tile of frame t gets the shift within +-r pixels of the pair's drift under which the tile's foreground
+        lies on most foreground of frame t - 1 (``pick_flow``; an empty tile keeps the drift), the links are taken under
+        that field, and flow_y / flow_x follow the drift columns: the field value of the tile that holds the cell's
+        centroid pixel, i.e. the cell's estimated motion against the previous frame, stage drift included (0 in frame 0).
+        drift_y / drift_x and the registered centroids stay the global ones.  Whole pixels, one shift per tile: no
+        smoothing or interpolation of the field, no rotation, no per-cell search, no gap closing.  Needs ``drift``.
+    :param flow_tile: 64 (default), 128 or 256: the tile edge in pixels.  Small tiles follow a steep field, large tiles
+        hold more cells to vote.  Read only with ``flow``.
     :param hull: True: the table ends with the measures of every cell's pixel outline (HULL_COLUMNS): the crack perimeter,
         the area of the convex hull of the pixel corners and the solidity, the largest caliper (Feret diameter) with its
         angle and end points, and the smallest caliper.  The cell is the union of its pixel squares: no sub-pixel contour
@@ -1011,9 +1119,12 @@ def measure_cells(mask, img=None, channels=None, link=True, min_overlap=1, devic
     :param spot_scale: s, a whole number in 1 .. 5 (default 2): the band-pass is the difference of two binomial smoothings
         with sigma = sqrt(s / 2) and sqrt(s) pixels: foci of about that radius answer best.  Read only with ``spots``.
     :return: pandas.DataFrame with the columns of ``columns(channels, link, drift is not None, hull, midline, percentiles,
-        neighbors is not None, spots is not None)``.
+        neighbors is not None, spots is not None, flow is not None)``.
     """
     drift = check_drift(drift)
+    flow, flow_tile = check_flow(flow, flow_tile)
+    if flow is not None and drift is None:
+        raise ValueError("flow searches around the stage drift of every frame pair: it needs drift")
     percentiles = check_percentiles(percentiles)
     neighbors = check_neighbors(neighbors)
     spots = check_spots(spots, spot_scale)
@@ -1045,7 +1156,11 @@ def measure_cells(mask, img=None, channels=None, link=True, min_overlap=1, devic
             raise ValueError("spots are taken of an image's channels: none is measured")
         raw = measure_raw(lab, pix, off, image, channels)
         shift = pick_drift(drift_raw(lab, pix, off, drift)) if drift is not None else None
-        links = link_raw(lab, pix, off, shift=shift) if link else None
+        field = pick_flow(flow_raw(lab, pix, off, shift, flow, flow_tile), shift) if flow is not None else None
+        if field is not None:
+            links = link_raw(lab, pix, off, field=field, tile=flow_tile)
+        else:
+            links = link_raw(lab, pix, off, shift=shift) if link else None
         outline = hull_raw(lab, pix, off, raw["bbox"]) if hull else None
         skel = midline_raw(lab, pix, off, raw["bbox"]) if midline else None
         stats = None
@@ -1055,7 +1170,8 @@ def measure_cells(mask, img=None, channels=None, link=True, min_overlap=1, devic
             stats = (percentiles,) + order_stats_raw(lab, pix, off, image, channels, raw["bbox"], ranks, bg_ranks)
         near = neighbors_raw(lab, pix, off, neighbors)[0] if neighbors is not None else None
         foci = (spots[1],) + spots_raw(lab, pix, off, image, channels, *spots) if spots is not None else None
-    return table_from_sums(off, H, W, raw, channels, links, min_overlap, shift, outline, skel, stats, near, foci)
+    return table_from_sums(off, H, W, raw, channels, links, min_overlap, shift, outline, skel, stats, near, foci, field,
+                           flow_tile if field is not None else None)
 
 
 def write_cells(df, csv_path):
