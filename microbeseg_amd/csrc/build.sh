@@ -11,7 +11,7 @@ pids=()
 for s in $SRCS; do
   o=../_build/${s%.hip}.o
   OBJS="$OBJS $o"
-  if [ ! -f "$o" ] || [ "$s" -nt "$o" ] || [ common.h -nt "$o" ] || [ igemm_common.h -nt "$o" ] || [ bf16_affine.h -nt "$o" ] || [ ../../include/mseg_hip.h -nt "$o" ]; then
+  if [ ! -f "$o" ] || [ "$s" -nt "$o" ] || [ common.h -nt "$o" ] || [ cell_common.h -nt "$o" ] || [ igemm_common.h -nt "$o" ] || [ bf16_affine.h -nt "$o" ] || [ ../../include/mseg_hip.h -nt "$o" ]; then
     # -pragma-unroll-threshold: the fully unrolled epilogues exceed LLVM's default 16k-instruction cap for "#pragma unroll";
     # a loop left rolled would index the accumulator array dynamically and push it to scratch memory
     # -fno-slp-vectorize for the matrix kernels: the SLP vectorizer turns the staging code's scalar fp32 multiply-adds into

@@ -8,7 +8,7 @@
 //   mseg_cell_links_shifted  the same with frame t - 1 moved by a per-pair integer shift (drift compensation, §6o)
 //   mseg_cell_links_field    the same with one integer shift per tile of frame t (tile-wise displacement field, §6v)
 // Everything is integer arithmetic with order-free 64-bit atomics: bit-identical from run to run.
-#include "common.h"
+#include "cell_common.h"
 
 #define CM_BLOCK 256
 #define CM_WAVES (CM_BLOCK / 64)
@@ -18,10 +18,6 @@
 #define CL_MIN_CAP 64
 
 namespace {
-
-typedef unsigned long long u64;
-
-inline size_t cl_align(size_t v) { return (v + 255) / 256 * 256; }
 
 // ---- a. measure ---------------------------------------------------------------------------------------------------------
 struct CmOut {
@@ -123,27 +119,6 @@ __device__ __forceinline__ void cm_flush_bg(const CmOut& o, int t, u64 cnt, cons
   }
 }
 
-template <typename E>
-__device__ __forceinline__ void cm_load8(const E* __restrict__ p, int nvalid, int64_t stride, bool vec, int (&v)[CM_PPL]) {
-  if (vec) {                                     // CM_PPL contiguous elements at a 16-byte (8 for uint8) aligned address
-    if (sizeof(E) == 4) {
-      const int4 a = *reinterpret_cast<const int4*>(p), b = *reinterpret_cast<const int4*>(p + 4);
-      v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-    } else if (sizeof(E) == 2) {
-      const uint4 a = *reinterpret_cast<const uint4*>(p);
-      v[0] = a.x & 0xFFFF; v[1] = a.x >> 16; v[2] = a.y & 0xFFFF; v[3] = a.y >> 16;
-      v[4] = a.z & 0xFFFF; v[5] = a.z >> 16; v[6] = a.w & 0xFFFF; v[7] = a.w >> 16;
-    } else {
-      const uint2 a = *reinterpret_cast<const uint2*>(p);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) { v[k] = (a.x >> (8 * k)) & 0xFF; v[4 + k] = (a.y >> (8 * k)) & 0xFF; }
-    }
-    return;
-  }
-#pragma unroll
-  for (int k = 0; k < CM_PPL; ++k) v[k] = k < nvalid ? (int)p[(int64_t)k * stride] : 0;
-}
-
 // A wave owns a contiguous range of (frame, 512-pixel chunk) steps; a chunk never leaves its frame.  A lane folds its 8
 // pixels into horizontal runs of one label (a run ends at the row end).  Runs that stay inside the lane are added by the
 // lane; the piece at the lane's start that continues the previous lane's run ("head") is handed to the lane where that run
@@ -179,8 +154,7 @@ __global__ void __launch_bounds__(CM_BLOCK) cm_kernel(const L* __restrict__ lab,
     }
     const int nvalid = max(0, min(CM_PPL, HW - p0));
     int l[CM_PPL];
-    const L* lp = lab + (int64_t)t * HW + p0;
-    cm_load8<L>(lp, nvalid, 1, nvalid == CM_PPL && ((uintptr_t)lp & 15) == 0, l);
+    cell_load8<L>(lab + (int64_t)t * HW, p0, HW, l);
     int y = nvalid ? p0 / W : 0, x = nvalid ? p0 - y * W : 0;
     const int y_first = y, x_first = x;
     int v[NC > 0 ? NC : 1][CM_PPL];
@@ -189,8 +163,7 @@ __global__ void __launch_bounds__(CM_BLOCK) cm_kernel(const L* __restrict__ lab,
       for (int c = 0; c < NC; ++c) {
         const P* ip = img + (int64_t)t * fs + (int64_t)(ch0 + c) * cs;
         if (img_flat) {
-          ip += p0;
-          cm_load8<P>(ip, nvalid, 1, nvalid == CM_PPL && ((uintptr_t)ip & (sizeof(P) * CM_PPL - 1)) == 0, v[c]);
+          cell_load8<P>(ip, p0, HW, v[c]);
         } else {
           int yy = y, xx = x;
 #pragma unroll
@@ -204,7 +177,7 @@ __global__ void __launch_bounds__(CM_BLOCK) cm_kernel(const L* __restrict__ lab,
     // run label of a pixel: its id if the frame's table holds it, else 0 (no run); background is the raw label 0
     int e[CM_PPL];
 #pragma unroll
-    for (int k = 0; k < CM_PPL; ++k) e[k] = (k < nvalid && l[k] > 0 && (int64_t)l[k] <= K) ? l[k] : 0;
+    for (int k = 0; k < CM_PPL; ++k) e[k] = cell_id(l[k], K);       // 0 past the frame's end
     const int prev_last = __shfl_up(e[CM_PPL - 1], 1, 64);
     const bool link_in = lane > 0 && e[0] > 0 && prev_last == e[0] && x_first != 0;
     const unsigned long long links = __ballot(link_in);
@@ -302,27 +275,33 @@ void cm_launch(int nc, unsigned grid, hipStream_t st, const void* lab, int T, in
 }
 
 // ---- b. links -------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t cl_hash(uint32_t l, uint32_t m) {
-  uint32_t h = l * 0x9E3779B1u ^ m * 0x85EBCA77u;
-  h ^= h >> 15; h *= 0x2C1B3C6Du; h ^= h >> 13;
-  return h;
-}
-
 // len pixels of the pair (l, m) into the open-addressing table of one frame pair; a full table sets the pair's status
 __device__ __forceinline__ void cl_insert(u64* __restrict__ keys, uint32_t* __restrict__ cnt, uint32_t mask, uint32_t l,
                                           uint32_t m, uint32_t len, int32_t* __restrict__ status) {
-  const u64 key = (u64)l << 32 | m;
-  uint32_t h = cl_hash(l, m) & mask;
-  for (uint32_t probe = 0; probe <= mask; ++probe) {
-    u64 k = keys[h];
-    if (k == 0) k = atomicCAS(&keys[h], 0ull, key);
-    if (k == 0 || k == key) { atomicAdd(&cnt[h], len); return; }
-    h = (h + 1) & mask;
-  }
-  atomicOr(status, 1);
+  const uint32_t h = cell_pair_slot<false>(keys, mask, l, m, status);
+  if (h <= mask) atomicAdd(&cnt[h], len);
 }
 
-// A lane folds 8 consecutive pixels of frames t - 1 and t into runs of one (l, m) pair: one insert and one add per run
+// a lane's 8 pixels of frame t (l) and the pixels of frame t - 1 under them (m), folded into runs of one pair of cells: one
+// insert per run.  Pixels past the frame's (the row's) end are 0 in l.
+__device__ __forceinline__ void cl_fold8(const int (&l)[CM_PPL], const int (&m)[CM_PPL], const int64_t* __restrict__ loff,
+                                         int t, u64* __restrict__ keys, uint32_t* __restrict__ cnt, uint32_t cap,
+                                         int32_t* __restrict__ status) {
+  const int64_t Kl = loff[t + 1] - loff[t], Km = loff[t] - loff[t - 1];
+  u64* kt = keys + (size_t)(t - 1) * cap;
+  uint32_t* ct = cnt + (size_t)(t - 1) * cap;
+  int cl = 0, cm = 0;
+  uint32_t len = 0;
+#pragma unroll
+  for (int k = 0; k < CM_PPL; ++k) {
+    const bool ok = cell_id(l[k], Kl) && cell_id(m[k], Km);
+    if (len && (!ok || l[k] != cl || m[k] != cm)) { cl_insert(kt, ct, cap - 1, cl, cm, len, status + t); len = 0; }
+    if (ok) { cl = l[k]; cm = m[k]; ++len; }
+  }
+  if (len) cl_insert(kt, ct, cap - 1, cl, cm, len, status + t);
+}
+
+// A lane folds 8 consecutive pixels of frames t - 1 and t (flat order: both loads are aligned whenever the frames are)
 template <typename L>
 __global__ void __launch_bounds__(CM_BLOCK) cl_pairs_kernel(const L* __restrict__ lab, int T, int HW,
                                                             const int64_t* __restrict__ loff, u64* __restrict__ keys,
@@ -333,24 +312,10 @@ __global__ void __launch_bounds__(CM_BLOCK) cl_pairs_kernel(const L* __restrict_
   if (g >= (int64_t)(T - 1) * groups) return;
   const int t = (int)(g / groups) + 1;
   const int p0 = (int)(g - (int64_t)(t - 1) * groups) * CM_PPL;
-  const int nvalid = min(CM_PPL, HW - p0);
-  const int64_t Kl = loff[t + 1] - loff[t], Km = loff[t] - loff[t - 1];
-  const L* pl = lab + (int64_t)t * HW + p0;
-  const L* pm = pl - HW;
   int l[CM_PPL], m[CM_PPL];
-  cm_load8<L>(pl, nvalid, 1, nvalid == CM_PPL && ((uintptr_t)pl & 15) == 0, l);
-  cm_load8<L>(pm, nvalid, 1, nvalid == CM_PPL && ((uintptr_t)pm & 15) == 0, m);
-  u64* kt = keys + (size_t)(t - 1) * cap;
-  uint32_t* ct = cnt + (size_t)(t - 1) * cap;
-  int cl = 0, cm = 0;
-  uint32_t len = 0;
-#pragma unroll
-  for (int k = 0; k < CM_PPL; ++k) {
-    const bool ok = k < nvalid && l[k] > 0 && (int64_t)l[k] <= Kl && m[k] > 0 && (int64_t)m[k] <= Km;
-    if (len && (!ok || l[k] != cl || m[k] != cm)) { cl_insert(kt, ct, cap - 1, cl, cm, len, status + t); len = 0; }
-    if (ok) { cl = l[k]; cm = m[k]; ++len; }
-  }
-  if (len) cl_insert(kt, ct, cap - 1, cl, cm, len, status + t);
+  cell_load8<L>(lab + (int64_t)t * HW, p0, HW, l);
+  cell_load8<L>(lab + (int64_t)(t - 1) * HW, p0, HW, m);
+  cl_fold8(l, m, loff, t, keys, cnt, cap, status);
 }
 
 // The pairs under a per-pair shift: pixel (y, x) of frame t pairs with (y - dy_t, x - dx_t) of frame t - 1.  A lane folds 8
@@ -376,27 +341,15 @@ __global__ void __launch_bounds__(CM_BLOCK) cl_pairs_shifted_kernel(const L* __r
   const int64_t ys = (int64_t)y - shift[2 * at], xs0 = (int64_t)x0 - shift[2 * at + 1];
   if (ys < 0 || ys >= H || xs0 + CM_PPL <= 0 || xs0 >= W) return;      // no pixel of this lane has a source
   const int nvalid = min(CM_PPL, W - x0);
-  const int64_t Kl = loff[t + 1] - loff[t], Km = loff[t] - loff[t - 1];
-  const L* pl = lab + ((int64_t)t * H + y) * W + x0;
   const L* pm = lab + ((int64_t)(t - 1) * H + ys) * W;                  // the source row
   int l[CM_PPL], m[CM_PPL];
-  cm_load8<L>(pl, nvalid, 1, nvalid == CM_PPL && ((uintptr_t)pl & 15) == 0, l);
+  cell_load8<L>(lab + ((int64_t)t * H + y) * W, x0, W, l);
 #pragma unroll
   for (int k = 0; k < CM_PPL; ++k) {
     const int64_t xs = xs0 + k;
     m[k] = (k < nvalid && xs >= 0 && xs < W) ? (int)pm[xs] : 0;
   }
-  u64* kt = keys + (size_t)(t - 1) * cap;
-  uint32_t* ct = cnt + (size_t)(t - 1) * cap;
-  int cl = 0, cm = 0;
-  uint32_t len = 0;
-#pragma unroll
-  for (int k = 0; k < CM_PPL; ++k) {
-    const bool ok = k < nvalid && l[k] > 0 && (int64_t)l[k] <= Kl && m[k] > 0 && (int64_t)m[k] <= Km;
-    if (len && (!ok || l[k] != cl || m[k] != cm)) { cl_insert(kt, ct, cap - 1, cl, cm, len, status + t); len = 0; }
-    if (ok) { cl = l[k]; cm = m[k]; ++len; }
-  }
-  if (len) cl_insert(kt, ct, cap - 1, cl, cm, len, status + t);
+  cl_fold8(l, m, loff, t, keys, cnt, cap, status);
 }
 
 // every table entry: best[cell] = max(count << 32 | ~m): the largest overlap, ties to the smallest m
@@ -420,8 +373,6 @@ __global__ void cl_out_kernel(const u64* __restrict__ best, int64_t n, int32_t* 
   overlap[s] = (int32_t)(b >> 32);
 }
 
-inline unsigned cl_blocks(int64_t n) { return (unsigned)((n + CM_BLOCK - 1) / CM_BLOCK < 1 ? 1 : (n + CM_BLOCK - 1) / CM_BLOCK); }
-
 }  // namespace
 
 // ---- entry points -----------------------------------------------------------------------------------------------------------
@@ -430,11 +381,9 @@ extern "C" int mseg_cell_measure(const void* labels, int label_dtype, int T, int
                                  int64_t chan_stride, int64_t row_stride, int64_t pix_stride, uint64_t* shape,
                                  int32_t* bbox, uint64_t* ch_sums, uint32_t* ch_minmax, uint64_t* bg_sums,
                                  uint32_t* bg_minmax, void* stream) {
-  if (!labels || !label_off || T <= 0 || H <= 0 || W <= 0 || n_labels < 0 || C < 0) return MSEG_EINVAL;
-  if ((int64_t)H * W >= (1ll << 31) - CM_CHUNK) return MSEG_EINVAL;
-  if (label_dtype != MSEG_PIX_U16 && label_dtype != MSEG_PIX_I32) return MSEG_EINVAL;
+  if (!cell_stack_ok(labels, label_off, label_dtype, T, H, W, CM_CHUNK) || n_labels < 0 || C < 0) return MSEG_EINVAL;
   if (!img) C = 0;
-  if (C > 0 && img_dtype != MSEG_PIX_U8 && img_dtype != MSEG_PIX_U16) return MSEG_EINVAL;
+  if (C > 0 && !cell_image_ok(img_dtype)) return MSEG_EINVAL;
   if (C > 0 && (!bg_sums || !bg_minmax)) return MSEG_EINVAL;
   if (n_labels > 0 && (!shape || !bbox || (C > 0 && (!ch_sums || !ch_minmax)))) return MSEG_EINVAL;
   if (n_labels == 0 && C == 0) return MSEG_OK;
@@ -446,7 +395,7 @@ extern "C" int mseg_cell_measure(const void* labels, int label_dtype, int T, int
   int64_t items = 6 * n_labels;
   if (2 * C * n_labels > items) items = 2 * C * n_labels;
   if (3 * tc > items) items = 3 * tc;
-  hipLaunchKernelGGL(cm_init_kernel, dim3(cl_blocks(items)), dim3(CM_BLOCK), 0, st, o);
+  hipLaunchKernelGGL(cm_init_kernel, dim3(mseg_blocks(items, CM_BLOCK)), dim3(CM_BLOCK), 0, st, o);
   const int64_t steps = (int64_t)T * (((int64_t)H * W + CM_CHUNK - 1) / CM_CHUNK);
   // at most 4 workgroups per compute unit's worth of waves: every wave flushes its background sums once per frame it
   // meets, so fewer, longer waves keep those same-address atomics few
@@ -456,25 +405,15 @@ extern "C" int mseg_cell_measure(const void* labels, int label_dtype, int T, int
   do {
     const int nc = C - ch0 > CM_MAXC ? CM_MAXC : C - ch0;
     const int sh = ch0 == 0;
-    if (label_dtype == MSEG_PIX_U16) {
-      if (img_dtype == MSEG_PIX_U8 && nc > 0)
-        cm_launch<uint16_t, uint8_t>(nc, grid, st, labels, T, H, W, label_off, img, frame_stride, chan_stride, row_stride,
-                                     pix_stride, ch0, sh, o);
-      else
-        cm_launch<uint16_t, uint16_t>(nc, grid, st, labels, T, H, W, label_off, img, frame_stride, chan_stride, row_stride,
-                                      pix_stride, ch0, sh, o);
-    } else {
-      if (img_dtype == MSEG_PIX_U8 && nc > 0)
-        cm_launch<int32_t, uint8_t>(nc, grid, st, labels, T, H, W, label_off, img, frame_stride, chan_stride, row_stride,
-                                    pix_stride, ch0, sh, o);
-      else
-        cm_launch<int32_t, uint16_t>(nc, grid, st, labels, T, H, W, label_off, img, frame_stride, chan_stride, row_stride,
-                                     pix_stride, ch0, sh, o);
-    }
+    // without channels the image type is not checked and not used: the uint16 instantiation
+    cell_dispatch(label_dtype, nc > 0 ? img_dtype : MSEG_PIX_U16, [&](auto l, auto p) {
+      cm_launch<decltype(l), decltype(p)>(nc, grid, st, labels, T, H, W, label_off, img, frame_stride, chan_stride,
+                                          row_stride, pix_stride, ch0, sh, o);
+    });
     ch0 += nc;
   } while (ch0 < C);
   int64_t fin = n_labels > tc ? n_labels : tc;
-  hipLaunchKernelGGL(cm_finish_kernel, dim3(cl_blocks(fin)), dim3(CM_BLOCK), 0, st, o);
+  hipLaunchKernelGGL(cm_finish_kernel, dim3(mseg_blocks(fin, CM_BLOCK)), dim3(CM_BLOCK), 0, st, o);
   MSEG_LAUNCH_CHECK();
   return MSEG_OK;
 }
@@ -482,102 +421,76 @@ extern "C" int mseg_cell_measure(const void* labels, int label_dtype, int T, int
 extern "C" size_t mseg_cell_links_workspace_bytes(int T, int64_t n_labels, int64_t table_cap) {
   if (T <= 0 || n_labels < 0 || table_cap < CL_MIN_CAP || table_cap > (1ll << 31) || (table_cap & (table_cap - 1))) return 0;
   const size_t pairs = (size_t)(T > 1 ? T - 1 : 1);
-  return cl_align(pairs * (size_t)table_cap * sizeof(u64)) + cl_align(pairs * (size_t)table_cap * sizeof(uint32_t)) +
-         cl_align((size_t)(n_labels + 1) * sizeof(u64));
+  return mseg_align256(pairs * (size_t)table_cap * sizeof(u64)) + mseg_align256(pairs * (size_t)table_cap * sizeof(uint32_t)) +
+         mseg_align256((size_t)(n_labels + 1) * sizeof(u64));
+}
+
+// The three links calls.  shift == nullptr: same (y, x) in both frames (cl_pairs_kernel: both frames by vector loads);
+// tile == 0: shift is [T][2], one (dy, dx) per frame pair; else [T][ty][tx][2], one per tile x tile pixels of frame t
+static int cl_links(const void* labels, int dtype, int T, int H, int W, const int64_t* label_off, int64_t n_labels,
+                    int64_t table_cap, const int32_t* shift, int tile, int32_t* pred, int32_t* overlap, int32_t* status,
+                    void* ws, size_t ws_bytes, void* stream) {
+  if (!cell_stack_ok(labels, label_off, dtype, T, H, W, CM_PPL) || !status || !ws || n_labels < 0) return MSEG_EINVAL;
+  if (n_labels > 0 && (!pred || !overlap)) return MSEG_EINVAL;
+  const size_t need = mseg_cell_links_workspace_bytes(T, n_labels, table_cap);
+  if (need == 0) return MSEG_EINVAL;
+  if (ws_bytes < need) return MSEG_EWORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  if (hipMemsetAsync(status, 0, sizeof(int32_t) * (size_t)T, st) != hipSuccess) return MSEG_ELAUNCH;
+  if (n_labels == 0) return MSEG_OK;
+  const size_t pairs = (size_t)(T > 1 ? T - 1 : 1);
+  const uint32_t cap = (uint32_t)table_cap;
+  char* b = (char*)ws;
+  u64* keys = (u64*)b;
+  uint32_t* cnt = (uint32_t*)(b + mseg_align256(pairs * (size_t)cap * sizeof(u64)));
+  u64* best = (u64*)((char*)cnt + mseg_align256(pairs * (size_t)cap * sizeof(uint32_t)));
+  if (hipMemsetAsync(ws, 0, need, st) != hipSuccess) return MSEG_ELAUNCH;
+  if (T > 1) {
+    // lanes: 8 pixels each, in flat order without a shift, row by row with one
+    const int64_t lanes = shift ? (int64_t)(T - 1) * H * (((int64_t)W + CM_PPL - 1) / CM_PPL)
+                                : (int64_t)(T - 1) * (((int64_t)H * W + CM_PPL - 1) / CM_PPL);
+    const dim3 grid(mseg_blocks(lanes, CM_BLOCK)), block(CM_BLOCK);
+    cell_dispatch(dtype, [&](auto l) {
+      typedef decltype(l) L;
+      const L* lab = (const L*)labels;
+      if (!shift)
+        hipLaunchKernelGGL(cl_pairs_kernel<L>, grid, block, 0, st, lab, T, H * W, label_off, keys, cnt, cap, status);
+      else if (tile)
+        hipLaunchKernelGGL((cl_pairs_shifted_kernel<L, true>), grid, block, 0, st, lab, T, H, W, label_off, shift, tile, keys,
+                           cnt, cap, status);
+      else
+        hipLaunchKernelGGL((cl_pairs_shifted_kernel<L, false>), grid, block, 0, st, lab, T, H, W, label_off, shift, tile, keys,
+                           cnt, cap, status);
+    });
+    const int64_t entries = (int64_t)(T - 1) * cap;
+    hipLaunchKernelGGL(cl_best_kernel, dim3(mseg_blocks(entries, CM_BLOCK)), block, 0, st, (const u64*)keys,
+                       (const uint32_t*)cnt, entries, cap, label_off, best);
+  }
+  hipLaunchKernelGGL(cl_out_kernel, dim3(mseg_blocks(n_labels, CM_BLOCK)), dim3(CM_BLOCK), 0, st, (const u64*)best, n_labels,
+                     pred, overlap);
+  MSEG_LAUNCH_CHECK();
+  return MSEG_OK;
 }
 
 extern "C" int mseg_cell_links(const void* labels, int dtype, int T, int H, int W, const int64_t* label_off,
                                int64_t n_labels, int64_t table_cap, int32_t* pred, int32_t* overlap, int32_t* status,
                                void* ws, size_t ws_bytes, void* stream) {
-  if (!labels || !label_off || !status || !ws || T <= 0 || H <= 0 || W <= 0 || n_labels < 0) return MSEG_EINVAL;
-  if ((int64_t)H * W >= (1ll << 31) - CM_PPL) return MSEG_EINVAL;
-  if (dtype != MSEG_PIX_U16 && dtype != MSEG_PIX_I32) return MSEG_EINVAL;
-  if (n_labels > 0 && (!pred || !overlap)) return MSEG_EINVAL;
-  const size_t need = mseg_cell_links_workspace_bytes(T, n_labels, table_cap);
-  if (need == 0) return MSEG_EINVAL;
-  if (ws_bytes < need) return MSEG_EWORKSPACE;
-  hipStream_t st = (hipStream_t)stream;
-  if (hipMemsetAsync(status, 0, sizeof(int32_t) * (size_t)T, st) != hipSuccess) return MSEG_ELAUNCH;
-  if (n_labels == 0) return MSEG_OK;
-  const size_t pairs = (size_t)(T > 1 ? T - 1 : 1);
-  const uint32_t cap = (uint32_t)table_cap;
-  char* b = (char*)ws;
-  u64* keys = (u64*)b;
-  uint32_t* cnt = (uint32_t*)(b + cl_align(pairs * (size_t)cap * sizeof(u64)));
-  u64* best = (u64*)((char*)cnt + cl_align(pairs * (size_t)cap * sizeof(uint32_t)));
-  if (hipMemsetAsync(ws, 0, need, st) != hipSuccess) return MSEG_ELAUNCH;
-  if (T > 1) {
-    const int HW = H * W;
-    const int64_t lanes = (int64_t)(T - 1) * (((int64_t)HW + CM_PPL - 1) / CM_PPL);
-    if (dtype == MSEG_PIX_U16)
-      hipLaunchKernelGGL(cl_pairs_kernel<uint16_t>, dim3(cl_blocks(lanes)), dim3(CM_BLOCK), 0, st, (const uint16_t*)labels,
-                         T, HW, label_off, keys, cnt, cap, status);
-    else
-      hipLaunchKernelGGL(cl_pairs_kernel<int32_t>, dim3(cl_blocks(lanes)), dim3(CM_BLOCK), 0, st, (const int32_t*)labels, T,
-                         HW, label_off, keys, cnt, cap, status);
-    const int64_t entries = (int64_t)(T - 1) * cap;
-    hipLaunchKernelGGL(cl_best_kernel, dim3(cl_blocks(entries)), dim3(CM_BLOCK), 0, st, (const u64*)keys,
-                       (const uint32_t*)cnt, entries, cap, label_off, best);
-  }
-  hipLaunchKernelGGL(cl_out_kernel, dim3(cl_blocks(n_labels)), dim3(CM_BLOCK), 0, st, (const u64*)best, n_labels, pred,
-                     overlap);
-  MSEG_LAUNCH_CHECK();
-  return MSEG_OK;
-}
-
-// mseg_cell_links_shifted (tile == 0: shift is [T][2]) and mseg_cell_links_field (shift is [T][ty][tx][2])
-static int cl_links_moved(const void* labels, int dtype, int T, int H, int W, const int64_t* label_off, int64_t n_labels,
-                          int64_t table_cap, const int32_t* shift, int tile, int32_t* pred, int32_t* overlap,
-                          int32_t* status, void* ws, size_t ws_bytes, void* stream) {
-  if (!labels || !label_off || !shift || !status || !ws || T <= 0 || H <= 0 || W <= 0 || n_labels < 0) return MSEG_EINVAL;
-  if ((int64_t)H * W >= (1ll << 31) - CM_PPL) return MSEG_EINVAL;
-  if (dtype != MSEG_PIX_U16 && dtype != MSEG_PIX_I32) return MSEG_EINVAL;
-  if (n_labels > 0 && (!pred || !overlap)) return MSEG_EINVAL;
-  const size_t need = mseg_cell_links_workspace_bytes(T, n_labels, table_cap);
-  if (need == 0) return MSEG_EINVAL;
-  if (ws_bytes < need) return MSEG_EWORKSPACE;
-  hipStream_t st = (hipStream_t)stream;
-  if (hipMemsetAsync(status, 0, sizeof(int32_t) * (size_t)T, st) != hipSuccess) return MSEG_ELAUNCH;
-  if (n_labels == 0) return MSEG_OK;
-  const size_t pairs = (size_t)(T > 1 ? T - 1 : 1);
-  const uint32_t cap = (uint32_t)table_cap;
-  char* b = (char*)ws;
-  u64* keys = (u64*)b;
-  uint32_t* cnt = (uint32_t*)(b + cl_align(pairs * (size_t)cap * sizeof(u64)));
-  u64* best = (u64*)((char*)cnt + cl_align(pairs * (size_t)cap * sizeof(uint32_t)));
-  if (hipMemsetAsync(ws, 0, need, st) != hipSuccess) return MSEG_ELAUNCH;
-  if (T > 1) {
-    const int64_t lanes = (int64_t)(T - 1) * H * (((int64_t)W + CM_PPL - 1) / CM_PPL);
-#define CL_GO(L, FIELD)                                                                                                \
-  hipLaunchKernelGGL((cl_pairs_shifted_kernel<L, FIELD>), dim3(cl_blocks(lanes)), dim3(CM_BLOCK), 0, st, (const L*)labels, T, \
-                     H, W, label_off, shift, tile, keys, cnt, cap, status)
-    if (dtype == MSEG_PIX_U16) {
-      if (tile) CL_GO(uint16_t, true); else CL_GO(uint16_t, false);
-    } else {
-      if (tile) CL_GO(int32_t, true); else CL_GO(int32_t, false);
-    }
-#undef CL_GO
-    const int64_t entries = (int64_t)(T - 1) * cap;
-    hipLaunchKernelGGL(cl_best_kernel, dim3(cl_blocks(entries)), dim3(CM_BLOCK), 0, st, (const u64*)keys,
-                       (const uint32_t*)cnt, entries, cap, label_off, best);
-  }
-  hipLaunchKernelGGL(cl_out_kernel, dim3(cl_blocks(n_labels)), dim3(CM_BLOCK), 0, st, (const u64*)best, n_labels, pred,
-                     overlap);
-  MSEG_LAUNCH_CHECK();
-  return MSEG_OK;
+  return cl_links(labels, dtype, T, H, W, label_off, n_labels, table_cap, nullptr, 0, pred, overlap, status, ws, ws_bytes,
+                  stream);
 }
 
 extern "C" int mseg_cell_links_shifted(const void* labels, int dtype, int T, int H, int W, const int64_t* label_off,
                                        int64_t n_labels, int64_t table_cap, const int32_t* shift, int32_t* pred,
                                        int32_t* overlap, int32_t* status, void* ws, size_t ws_bytes, void* stream) {
-  return cl_links_moved(labels, dtype, T, H, W, label_off, n_labels, table_cap, shift, 0, pred, overlap, status, ws, ws_bytes,
-                        stream);
+  if (!shift) return MSEG_EINVAL;
+  return cl_links(labels, dtype, T, H, W, label_off, n_labels, table_cap, shift, 0, pred, overlap, status, ws, ws_bytes,
+                  stream);
 }
 
 extern "C" int mseg_cell_links_field(const void* labels, int dtype, int T, int H, int W, const int64_t* label_off,
                                      int64_t n_labels, int64_t table_cap, int tile, const int32_t* field, int32_t* pred,
                                      int32_t* overlap, int32_t* status, void* ws, size_t ws_bytes, void* stream) {
-  if (tile != 64 && tile != 128 && tile != 256) return MSEG_EINVAL;
-  return cl_links_moved(labels, dtype, T, H, W, label_off, n_labels, table_cap, field, tile, pred, overlap, status, ws,
-                        ws_bytes, stream);
+  if (!field || (tile != 64 && tile != 128 && tile != 256)) return MSEG_EINVAL;
+  return cl_links(labels, dtype, T, H, W, label_off, n_labels, table_cap, field, tile, pred, overlap, status, ws, ws_bytes,
+                  stream);
 }

@@ -8,7 +8,7 @@
 // Two kernels each: the labels are packed into one foreground bit per pixel once (dr_pack_kernel), the scores are popcounts of
 // ANDed 64-bit words of those bit rows (dr_score_kernel; per tile from LDS: fl_score_kernel), 64 pixels per operation.
 // Integer atomics (dr_score_kernel) or one plain store per score (fl_score_kernel): bit-identical from run to run.
-#include "common.h"
+#include "cell_common.h"
 
 #define DR_BLOCK 256
 #define DR_WAVES (DR_BLOCK / 64)
@@ -24,9 +24,6 @@
 
 namespace {
 
-typedef unsigned long long u64;
-
-inline size_t dr_align(size_t v) { return (v + 255) / 256 * 256; }
 inline int dr_words(int W) { return (W + 63) / 64; }
 inline int64_t dr_row_stride(int W) { return (int64_t)dr_words(W) + DR_PAD_L + DR_PAD_R; }
 
@@ -47,9 +44,9 @@ __global__ void __launch_bounds__(DR_BLOCK) dr_pack_kernel(const L* __restrict__
       const int t = (int)(row / H);
       const int64_t K = loff[t + 1] - loff[t];
       const int x = j * 64 + lane;
-      int64_t id = 0;
-      if (x < W) id = (int64_t)lab[row * W + x];
-      word = __ballot(id > 0 && id <= K);
+      int id = 0;
+      if (x < W) id = (int)lab[row * W + x];
+      word = __ballot(cell_id(id, K) != 0);
     }
     if (lane == 0) bits[i] = word;
   }
@@ -166,26 +163,23 @@ void dr_pack(const void* labels, int dtype, int T, int H, int W, const int64_t* 
   const int64_t words = (int64_t)T * H * dr_row_stride(W);
   int64_t grid = (words + DR_WAVES - 1) / DR_WAVES;
   if (grid > DR_MAX_GRID) grid = DR_MAX_GRID;
-  if (dtype == MSEG_PIX_U16)
-    hipLaunchKernelGGL(dr_pack_kernel<uint16_t>, dim3((unsigned)grid), dim3(DR_BLOCK), 0, st, (const uint16_t*)labels, T, H,
-                       W, label_off, bits);
-  else
-    hipLaunchKernelGGL(dr_pack_kernel<int32_t>, dim3((unsigned)grid), dim3(DR_BLOCK), 0, st, (const int32_t*)labels, T, H, W,
-                       label_off, bits);
+  cell_dispatch(dtype, [&](auto l) {
+    typedef decltype(l) L;
+    hipLaunchKernelGGL(dr_pack_kernel<L>, dim3((unsigned)grid), dim3(DR_BLOCK), 0, st, (const L*)labels, T, H, W, label_off,
+                       bits);
+  });
 }
 
 }  // namespace
 
 extern "C" size_t mseg_stack_drift_workspace_bytes(int T, int H, int W) {
   if (T <= 0 || H <= 0 || W <= 0 || (int64_t)H * W >= (1ll << 31) - 512) return 0;
-  return dr_align((size_t)T * (size_t)H * (size_t)dr_row_stride(W) * sizeof(u64));
+  return mseg_align256((size_t)T * (size_t)H * (size_t)dr_row_stride(W) * sizeof(u64));
 }
 
 extern "C" int mseg_stack_drift(const void* labels, int dtype, int T, int H, int W, const int64_t* label_off, int max_drift,
                                 uint32_t* scores, void* ws, size_t ws_bytes, void* stream) {
-  if (!labels || !label_off || !ws || T <= 0 || H <= 0 || W <= 0) return MSEG_EINVAL;
-  if ((int64_t)H * W >= (1ll << 31) - 512) return MSEG_EINVAL;
-  if (dtype != MSEG_PIX_U16 && dtype != MSEG_PIX_I32) return MSEG_EINVAL;
+  if (!cell_stack_ok(labels, label_off, dtype, T, H, W, 512) || !ws) return MSEG_EINVAL;
   if (max_drift < 0 || max_drift > DR_MAX_R) return MSEG_EINVAL;
   if (T > 1 && !scores) return MSEG_EINVAL;
   if (ws_bytes < mseg_stack_drift_workspace_bytes(T, H, W)) return MSEG_EWORKSPACE;
@@ -215,9 +209,7 @@ extern "C" size_t mseg_stack_flow_workspace_bytes(int T, int H, int W) { return 
 
 extern "C" int mseg_stack_flow(const void* labels, int dtype, int T, int H, int W, const int64_t* label_off, int tile,
                                int radius, const int32_t* base, uint32_t* scores, void* ws, size_t ws_bytes, void* stream) {
-  if (!labels || !label_off || !base || !ws || T <= 0 || H <= 0 || W <= 0) return MSEG_EINVAL;
-  if ((int64_t)H * W >= (1ll << 31) - 512) return MSEG_EINVAL;
-  if (dtype != MSEG_PIX_U16 && dtype != MSEG_PIX_I32) return MSEG_EINVAL;
+  if (!cell_stack_ok(labels, label_off, dtype, T, H, W, 512) || !base || !ws) return MSEG_EINVAL;
   if (tile != 64 && tile != 128 && tile != 256) return MSEG_EINVAL;
   if (radius < 0 || radius > FL_MAX_R) return MSEG_EINVAL;
   if (T > 1 && !scores) return MSEG_EINVAL;

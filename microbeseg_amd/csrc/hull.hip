@@ -7,7 +7,7 @@
 //   ch_hull_kernel   one wave per cell: the two monotone chains over the row extents, then shoelace, the farthest vertex
 //                    pair and the smallest width over the hull edges, spread over the lanes
 // Integers only, order-free atomics: bit-identical from run to run.
-#include "common.h"
+#include "cell_common.h"
 
 #define CH_BLOCK 256
 #define CH_WAVES (CH_BLOCK / 64)
@@ -15,11 +15,7 @@
 
 namespace {
 
-typedef unsigned long long u64;
 typedef unsigned __int128 u128;
-
-inline size_t ch_align(size_t v) { return (v + 255) / 256 * 256; }
-inline unsigned ch_blocks(int64_t n) { return (unsigned)((n + CH_BLOCK - 1) / CH_BLOCK < 1 ? 1 : (n + CH_BLOCK - 1) / CH_BLOCK); }
 
 struct ChWs {
   int32_t* xmin;      // [n_rows]  smallest corner column of a corner row, INT32_MAX: the cell has no pixel beside the row
@@ -32,34 +28,12 @@ inline ChWs ch_carve(void* ws, int64_t n_rows) {
   char* b = (char*)ws;
   ChWs w;
   w.xmin = (int32_t*)b;
-  w.xmax = (int32_t*)(b + ch_align(r * sizeof(int32_t)));
-  w.hv = (int2*)(b + 2 * ch_align(r * sizeof(int32_t)));
+  w.xmax = (int32_t*)(b + mseg_align256(r * sizeof(int32_t)));
+  w.hv = (int2*)(b + 2 * mseg_align256(r * sizeof(int32_t)));
   return w;
 }
 
 // ---- a. label pass ------------------------------------------------------------------------------------------------------
-// 8 elements of one frame from flat index q0 on; elements outside 0 .. HW - 1 read as 0 ("not a cell")
-template <typename L>
-__device__ __forceinline__ void ch_load8(const L* __restrict__ frame, int64_t q0, int HW, int (&v)[CH_PPL]) {
-  const L* p = frame + q0;
-  if (q0 >= 0 && q0 + CH_PPL <= HW && ((uintptr_t)p & 15) == 0) {
-    if (sizeof(L) == 4) {
-      const int4 a = *reinterpret_cast<const int4*>(p), b = *reinterpret_cast<const int4*>(p + 4);
-      v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-    } else {
-      const uint4 a = *reinterpret_cast<const uint4*>(p);
-      v[0] = a.x & 0xFFFF; v[1] = a.x >> 16; v[2] = a.y & 0xFFFF; v[3] = a.y >> 16;
-      v[4] = a.z & 0xFFFF; v[5] = a.z >> 16; v[6] = a.w & 0xFFFF; v[7] = a.w >> 16;
-    }
-    return;
-  }
-#pragma unroll
-  for (int k = 0; k < CH_PPL; ++k) {
-    const int64_t q = q0 + k;
-    v[k] = (q >= 0 && q < HW) ? (int)frame[q] : 0;
-  }
-}
-
 // A lane owns 8 consecutive pixels of a frame (flat order, so the loads are aligned whenever the frame is).  Its left and
 // right neighbours are the pixels before and after the 8, the upper and lower ones the same 8 positions one row up / down:
 // the neighbouring lanes' and rows' loads, served from cache.  A pixel whose left (right) neighbour is not of its cell is a
@@ -81,19 +55,17 @@ __global__ void __launch_bounds__(CH_BLOCK) ch_label_kernel(const L* __restrict_
   const int64_t base = loff[t], K = loff[t + 1] - base;
   const L* frame = lab + (int64_t)t * HW;
   int e[CH_PPL], up[CH_PPL], dn[CH_PPL];
-  ch_load8<L>(frame, p0, HW, e);
+  cell_load8<L>(frame, p0, HW, e);
   bool any = false;
 #pragma unroll
   for (int k = 0; k < CH_PPL; ++k) {
-    e[k] = (e[k] > 0 && (int64_t)e[k] <= K) ? e[k] : 0;
+    e[k] = cell_id(e[k], K);
     any |= e[k] > 0;
   }
   if (!any) return;
-  ch_load8<L>(frame, (int64_t)p0 - W, HW, up);
-  ch_load8<L>(frame, (int64_t)p0 + W, HW, dn);
-  int el = p0 > 0 ? (int)frame[p0 - 1] : 0, er = p0 + CH_PPL < HW ? (int)frame[p0 + CH_PPL] : 0;
-  el = (el > 0 && (int64_t)el <= K) ? el : 0;
-  er = (er > 0 && (int64_t)er <= K) ? er : 0;
+  cell_load8<L>(frame, (int64_t)p0 - W, HW, up);     // outside the frame: 0, not a cell
+  cell_load8<L>(frame, (int64_t)p0 + W, HW, dn);
+  const int el = cell_id(p0 > 0 ? (int)frame[p0 - 1] : 0, K), er = cell_id(p0 + CH_PPL < HW ? (int)frame[p0 + CH_PPL] : 0, K);
   int y = p0 / W, x = p0 - y * W;
   int cur = 0;
   unsigned cnt = 0;
@@ -106,7 +78,7 @@ __global__ void __launch_bounds__(CH_BLOCK) ch_label_kernel(const L* __restrict_
       cnt = 0;
     }
     if (l > 0) {
-      const int u = (up[k] > 0 && (int64_t)up[k] <= K) ? up[k] : 0, d = (dn[k] > 0 && (int64_t)dn[k] <= K) ? dn[k] : 0;
+      const int u = cell_id(up[k], K), d = cell_id(dn[k], K);
       const int lf = x > 0 ? (k > 0 ? e[k > 0 ? k - 1 : 0] : el) : 0;
       const int rt = x < W - 1 ? (k < CH_PPL - 1 ? e[k < CH_PPL - 1 ? k + 1 : k] : er) : 0;
       const bool open_l = lf != l, open_r = rt != l;
@@ -286,15 +258,13 @@ __global__ void __launch_bounds__(CH_BLOCK) ch_hull_kernel(const int32_t* __rest
 extern "C" size_t mseg_cell_hull_workspace_bytes(int64_t n_labels, int64_t n_rows) {
   if (n_labels < 0 || n_rows < 0 || n_rows > (1ll << 40)) return 0;
   const size_t r = (size_t)(n_rows > 0 ? n_rows : 1);
-  return 2 * ch_align(r * sizeof(int32_t)) + ch_align(2 * r * sizeof(int2));
+  return 2 * mseg_align256(r * sizeof(int32_t)) + mseg_align256(2 * r * sizeof(int2));
 }
 
 extern "C" int mseg_cell_hull(const void* labels, int dtype, int T, int H, int W, const int64_t* label_off,
                               int64_t n_labels, const int32_t* bbox, const int64_t* row_off, int64_t n_rows, int64_t* out,
                               int32_t* status, void* ws, size_t ws_bytes, void* stream) {
-  if (!labels || !label_off || !status || !ws || T <= 0 || H <= 0 || W <= 0 || n_labels < 0 || n_rows < 0) return MSEG_EINVAL;
-  if ((int64_t)H * W >= (1ll << 31) - 512) return MSEG_EINVAL;
-  if (dtype != MSEG_PIX_U16 && dtype != MSEG_PIX_I32) return MSEG_EINVAL;
+  if (!cell_stack_ok(labels, label_off, dtype, T, H, W, 512) || !status || !ws || n_labels < 0 || n_rows < 0) return MSEG_EINVAL;
   if (n_labels > 0 && (!bbox || !row_off || !out)) return MSEG_EINVAL;
   const size_t need = mseg_cell_hull_workspace_bytes(n_labels, n_rows);
   if (need == 0) return MSEG_EINVAL;
@@ -308,15 +278,15 @@ extern "C" int mseg_cell_hull(const void* labels, int dtype, int T, int H, int W
   }
   const ChWs w = ch_carve(ws, n_rows);
   const int64_t items = n_rows > n_labels ? n_rows : n_labels;
-  hipLaunchKernelGGL(ch_init_kernel, dim3(ch_blocks(items)), dim3(CH_BLOCK), 0, st, w.xmin, w.xmax, n_rows, out, n_labels,
+  const dim3 block(CH_BLOCK);
+  hipLaunchKernelGGL(ch_init_kernel, dim3(mseg_blocks(items, CH_BLOCK)), block, 0, st, w.xmin, w.xmax, n_rows, out, n_labels,
                      status);
-  if (dtype == MSEG_PIX_U16)
-    hipLaunchKernelGGL(ch_label_kernel<uint16_t>, dim3(ch_blocks(lanes)), dim3(CH_BLOCK), 0, st, (const uint16_t*)labels, T,
-                       H, W, label_off, bbox, row_off, n_rows, w.xmin, w.xmax, (u64*)out, status);
-  else
-    hipLaunchKernelGGL(ch_label_kernel<int32_t>, dim3(ch_blocks(lanes)), dim3(CH_BLOCK), 0, st, (const int32_t*)labels, T,
-                       H, W, label_off, bbox, row_off, n_rows, w.xmin, w.xmax, (u64*)out, status);
-  hipLaunchKernelGGL(ch_hull_kernel, dim3(ch_blocks(n_labels * 64)), dim3(CH_BLOCK), 0, st, bbox, row_off, n_labels, n_rows,
+  cell_dispatch(dtype, [&](auto l) {
+    typedef decltype(l) L;
+    hipLaunchKernelGGL(ch_label_kernel<L>, dim3(mseg_blocks(lanes, CH_BLOCK)), block, 0, st, (const L*)labels, T, H, W,
+                       label_off, bbox, row_off, n_rows, w.xmin, w.xmax, (u64*)out, status);
+  });
+  hipLaunchKernelGGL(ch_hull_kernel, dim3(mseg_blocks(n_labels * 64, CH_BLOCK)), block, 0, st, bbox, row_off, n_labels, n_rows,
                      (const int32_t*)w.xmin, (const int32_t*)w.xmax, w.hv, out, status);
   MSEG_LAUNCH_CHECK();
   return MSEG_OK;

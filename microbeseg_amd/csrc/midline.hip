@@ -19,7 +19,7 @@
 //                   one OR-fold per round; then, on the final bits, the counts, the end points, the scatter of the skeleton
 //                   image, and the distance search over the grown box in the labels themselves.
 // Integers only, order-free atomics (or / add / min / max): bit-identical from run to run.
-#include "common.h"
+#include "cell_common.h"
 
 #define MD_BLOCK 256               // lanes per group of the fill pass
 #define MD_GROUP 64                // lanes per group of the thin pass, one group per cell: a typical cell has ~20 words, larger
@@ -28,11 +28,6 @@
 #define MD_LDS_WORDS 512           // cells of up to this many words are thinned in LDS (2 x 4 KiB)
 
 namespace {
-
-typedef unsigned long long u64;
-
-inline size_t md_align(size_t v) { return (v + 255) / 256 * 256; }
-inline unsigned md_blocks(int64_t n) { return (unsigned)((n + MD_BLOCK - 1) / MD_BLOCK < 1 ? 1 : (n + MD_BLOCK - 1) / MD_BLOCK); }
 
 // the bit rows of one cell slot, from the box and the word table; ok: a present cell whose box and words are consistent
 struct MdCell {
@@ -57,24 +52,6 @@ __device__ __forceinline__ MdCell md_cell(const int32_t* __restrict__ bbox, cons
 }
 
 // ---- a. fill pass -------------------------------------------------------------------------------------------------------
-template <typename L>
-__device__ __forceinline__ void md_load8(const L* __restrict__ frame, int p0, int HW, int (&v)[MD_PPL]) {
-  const L* p = frame + p0;
-  if (p0 + MD_PPL <= HW && ((uintptr_t)p & 15) == 0) {
-    if (sizeof(L) == 4) {
-      const int4 a = *reinterpret_cast<const int4*>(p), b = *reinterpret_cast<const int4*>(p + 4);
-      v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-    } else {
-      const uint4 a = *reinterpret_cast<const uint4*>(p);
-      v[0] = a.x & 0xFFFF; v[1] = a.x >> 16; v[2] = a.y & 0xFFFF; v[3] = a.y >> 16;
-      v[4] = a.z & 0xFFFF; v[5] = a.z >> 16; v[6] = a.w & 0xFFFF; v[7] = a.w >> 16;
-    }
-    return;
-  }
-#pragma unroll
-  for (int k = 0; k < MD_PPL; ++k) v[k] = p0 + k < HW ? (int)frame[p0 + k] : 0;
-}
-
 // A lane owns 8 consecutive pixels of a frame (flat order).  The bits of a stretch that falls into one word of one cell go
 // out in one atomicOr.  A pixel outside the box given for its cell, or of a cell whose words do not match its box, is skipped
 // and sets bit 0 of the status word.
@@ -92,11 +69,11 @@ __global__ void __launch_bounds__(MD_BLOCK) md_fill_kernel(const L* __restrict__
   const int p0 = (int)(g - (int64_t)t * groups) * MD_PPL;
   const int64_t base = loff[t], K = loff[t + 1] - base;
   int e[MD_PPL];
-  md_load8<L>(lab + (int64_t)t * HW, p0, HW, e);
+  cell_load8<L>(lab + (int64_t)t * HW, p0, HW, e);
   bool any = false;
 #pragma unroll
   for (int k = 0; k < MD_PPL; ++k) {
-    e[k] = (e[k] > 0 && (int64_t)e[k] <= K) ? e[k] : 0;
+    e[k] = cell_id(e[k], K);
     any |= e[k] > 0;
   }
   if (!any) return;
@@ -355,15 +332,13 @@ __global__ void __launch_bounds__(MD_GROUP) md_thin_kernel(const L* __restrict__
 // ---- entry points -------------------------------------------------------------------------------------------------------
 extern "C" size_t mseg_cell_midline_workspace_bytes(int64_t n_labels, int64_t n_words) {
   if (n_labels < 0 || n_words < 0 || n_words > (1ll << 40)) return 0;
-  return 2 * md_align((size_t)(n_words > 0 ? n_words : 1) * sizeof(u64));
+  return 2 * mseg_align256((size_t)(n_words > 0 ? n_words : 1) * sizeof(u64));
 }
 
 extern "C" int mseg_cell_midline(const void* labels, int dtype, int T, int H, int W, const int64_t* label_off,
                                  int64_t n_labels, const int32_t* bbox, const int64_t* word_off, int64_t n_words,
                                  int64_t* out, uint8_t* skeleton, int32_t* status, void* ws, size_t ws_bytes, void* stream) {
-  if (!labels || !label_off || !status || !ws || T <= 0 || H <= 0 || W <= 0 || n_labels < 0 || n_words < 0) return MSEG_EINVAL;
-  if ((int64_t)H * W >= (1ll << 31) - 512) return MSEG_EINVAL;
-  if (dtype != MSEG_PIX_U16 && dtype != MSEG_PIX_I32) return MSEG_EINVAL;
+  if (!cell_stack_ok(labels, label_off, dtype, T, H, W, 512) || !status || !ws || n_labels < 0 || n_words < 0) return MSEG_EINVAL;
   if (n_labels > 0 && (!bbox || !word_off || !out)) return MSEG_EINVAL;
   const size_t need = mseg_cell_midline_workspace_bytes(n_labels, n_words);
   if (need == 0) return MSEG_EINVAL;
@@ -377,17 +352,13 @@ extern "C" int mseg_cell_midline(const void* labels, int dtype, int T, int H, in
   u64* bits_a = (u64*)ws;
   u64* bits_b = (u64*)((char*)ws + need / 2);
   if (hipMemsetAsync(bits_a, 0, need / 2, st) != hipSuccess) return MSEG_ELAUNCH;
-  if (dtype == MSEG_PIX_U16) {
-    hipLaunchKernelGGL(md_fill_kernel<uint16_t>, dim3(md_blocks(lanes)), dim3(MD_BLOCK), 0, st, (const uint16_t*)labels, T, H,
-                       W, label_off, bbox, word_off, n_words, bits_a, status);
-    hipLaunchKernelGGL(md_thin_kernel<uint16_t>, dim3((unsigned)n_labels), dim3(MD_GROUP), 0, st, (const uint16_t*)labels, T,
-                       H, W, label_off, n_labels, bbox, word_off, n_words, bits_a, bits_b, out, skeleton, status);
-  } else {
-    hipLaunchKernelGGL(md_fill_kernel<int32_t>, dim3(md_blocks(lanes)), dim3(MD_BLOCK), 0, st, (const int32_t*)labels, T, H,
-                       W, label_off, bbox, word_off, n_words, bits_a, status);
-    hipLaunchKernelGGL(md_thin_kernel<int32_t>, dim3((unsigned)n_labels), dim3(MD_GROUP), 0, st, (const int32_t*)labels, T,
-                       H, W, label_off, n_labels, bbox, word_off, n_words, bits_a, bits_b, out, skeleton, status);
-  }
+  cell_dispatch(dtype, [&](auto l) {
+    typedef decltype(l) L;
+    hipLaunchKernelGGL(md_fill_kernel<L>, dim3(mseg_blocks(lanes, MD_BLOCK)), dim3(MD_BLOCK), 0, st, (const L*)labels, T, H, W,
+                       label_off, bbox, word_off, n_words, bits_a, status);
+    hipLaunchKernelGGL(md_thin_kernel<L>, dim3((unsigned)n_labels), dim3(MD_GROUP), 0, st, (const L*)labels, T, H, W,
+                       label_off, n_labels, bbox, word_off, n_words, bits_a, bits_b, out, skeleton, status);
+  });
   MSEG_LAUNCH_CHECK();
   return MSEG_OK;
 }

@@ -10,7 +10,7 @@
 //   nb_table_kernel   one thread per table entry: the per-cell counts, nearest neighbour and main contact, the pair rows
 //   nb_finish_kernel  one thread per cell: unpacks the two packed planes
 // Integers only, order-free integer atomics: bit-identical from run to run (the order of the pair rows aside).
-#include "common.h"
+#include "cell_common.h"
 
 #define NB_BLOCK 256
 #define NB_TH 32                  // tile rows
@@ -21,11 +21,6 @@
 #define NB_CACHE 4                // neighbour ids a scanning lane keeps the best d2 of in registers
 
 namespace {
-
-typedef unsigned long long u64;
-
-inline size_t nb_align(size_t v) { return (v + 255) / 256 * 256; }
-inline unsigned nb_blocks(int64_t n) { return (unsigned)((n + NB_BLOCK - 1) / NB_BLOCK < 1 ? 1 : (n + NB_BLOCK - 1) / NB_BLOCK); }
 
 struct NbWs {
   u64* keys;          // [T][cap]  a << 32 | b with a < b, 0 = empty
@@ -40,13 +35,13 @@ inline NbWs nb_carve(void* ws, int T, int64_t n, int64_t cap) {
   char* b = (char*)ws;
   NbWs w;
   w.keys = (u64*)b;
-  b += nb_align(entries * sizeof(u64));
+  b += mseg_align256(entries * sizeof(u64));
   w.edges = (uint32_t*)b;
-  b += nb_align(entries * sizeof(uint32_t));
+  b += mseg_align256(entries * sizeof(uint32_t));
   w.d2 = (uint32_t*)b;
-  b += nb_align(entries * sizeof(uint32_t));
+  b += mseg_align256(entries * sizeof(uint32_t));
   w.nn = (u64*)b;
-  b += nb_align((size_t)(n + 1) * sizeof(u64));
+  b += mseg_align256((size_t)(n + 1) * sizeof(u64));
   w.best = (u64*)b;
   return w;
 }
@@ -65,30 +60,6 @@ __global__ void nb_init_kernel(NbWs w, int64_t entries, int64_t n, int64_t* __re
   if (i == 0) n_pairs[0] = 0;
 }
 
-__device__ __forceinline__ uint32_t nb_hash(uint32_t a, uint32_t b) {
-  uint32_t h = a * 0x9E3779B1u ^ b * 0x85EBCA77u;
-  h ^= h >> 15; h *= 0x2C1B3C6Du; h ^= h >> 13;
-  return h;
-}
-
-// the entry of the pair (a, b), a < b, in the open-addressing table of one frame, claimed if new; mask + 1: the table is full.
-// A long probe looks at the frame's status word every 32 steps and gives up once another lane found the table full: the
-// frame is redone anyway, and walking a full table to its end for every further pair would take longer than the redo.
-__device__ __forceinline__ uint32_t nb_find(u64* __restrict__ keys, uint32_t mask, uint32_t a, uint32_t b,
-                                            int32_t* __restrict__ status) {
-  const u64 key = (u64)a << 32 | b;
-  uint32_t h = nb_hash(a, b) & mask;
-  for (uint32_t probe = 0; probe <= mask; ++probe) {
-    u64 k = keys[h];
-    if (k == 0) k = atomicCAS(&keys[h], 0ull, key);
-    if (k == 0 || k == key) return h;
-    if ((probe & 31) == 31 && __hip_atomic_load(status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) return mask + 1;
-    h = (h + 1) & mask;
-  }
-  atomicOr(status, 1);
-  return mask + 1;
-}
-
 struct NbTable {
   u64* keys;
   uint32_t* edges;
@@ -97,16 +68,17 @@ struct NbTable {
   int32_t* status;
 };
 
+// a pair's entry in the frame's table: the slot of (the smaller, the larger id); a lane gives up early on a full table
 __device__ __forceinline__ void nb_add_edges(const NbTable& tb, int a, int b, uint32_t len) {
   const uint32_t lo = (uint32_t)min(a, b), hi = (uint32_t)max(a, b);
-  const uint32_t h = nb_find(tb.keys, tb.mask, lo, hi, tb.status);
+  const uint32_t h = cell_pair_slot<true>(tb.keys, tb.mask, lo, hi, tb.status);
   if (h <= tb.mask) atomicAdd(&tb.edges[h], len);
 }
 
 // d2 only ever falls, so a value read earlier is an upper bound of the entry: a candidate that does not beat it is dropped
 __device__ __forceinline__ void nb_min_d2(const NbTable& tb, int a, int b, uint32_t d2) {
   const uint32_t lo = (uint32_t)min(a, b), hi = (uint32_t)max(a, b);
-  const uint32_t h = nb_find(tb.keys, tb.mask, lo, hi, tb.status);
+  const uint32_t h = cell_pair_slot<true>(tb.keys, tb.mask, lo, hi, tb.status);
   if (h <= tb.mask && tb.d2[h] > d2) atomicMin(&tb.d2[h], d2);
 }
 
@@ -142,9 +114,9 @@ __global__ void __launch_bounds__(NB_BLOCK) nb_tile_kernel(const L* __restrict__
     const L* row = frame + (int64_t)(row_in ? gy : 0) * W;
     for (int lx = tid & 63; lx < LC; lx += 64) {
       const int gx = x0 - R + lx;
-      int64_t v = 0;
-      if (row_in && gx >= 0 && gx < W) v = (int64_t)row[gx];
-      tile[ly * LC + lx] = (E)((v > 0 && v <= K) ? v : 0);
+      int v = 0;
+      if (row_in && gx >= 0 && gx < W) v = (int)row[gx];
+      tile[ly * LC + lx] = (E)cell_id(v, K);
     }
   }
   __syncthreads();
@@ -310,17 +282,15 @@ extern "C" size_t mseg_cell_neighbors_workspace_bytes(int T, int64_t n_labels, i
   if (T <= 0 || n_labels < 0 || table_cap < NB_MIN_CAP || table_cap > (1ll << 31) || (table_cap & (table_cap - 1))) return 0;
   if ((int64_t)T * table_cap > (1ll << 40)) return 0;
   const size_t entries = (size_t)T * (size_t)table_cap;
-  return nb_align(entries * sizeof(u64)) + 2 * nb_align(entries * sizeof(uint32_t)) +
-         2 * nb_align((size_t)(n_labels + 1) * sizeof(u64));
+  return mseg_align256(entries * sizeof(u64)) + 2 * mseg_align256(entries * sizeof(uint32_t)) +
+         2 * mseg_align256((size_t)(n_labels + 1) * sizeof(u64));
 }
 
 extern "C" int mseg_cell_neighbors(const void* labels, int dtype, int T, int H, int W, const int64_t* label_off,
                                    int64_t n_labels, int radius, int64_t table_cap, int64_t* out, int32_t* pairs,
                                    int64_t pair_cap, int64_t* n_pairs, int32_t* status, void* ws, size_t ws_bytes,
                                    void* stream) {
-  if (!labels || !label_off || !status || !n_pairs || !ws || T <= 0 || H <= 0 || W <= 0 || n_labels < 0) return MSEG_EINVAL;
-  if ((int64_t)H * W >= (1ll << 31) - 512) return MSEG_EINVAL;
-  if (dtype != MSEG_PIX_U16 && dtype != MSEG_PIX_I32) return MSEG_EINVAL;
+  if (!cell_stack_ok(labels, label_off, dtype, T, H, W, 512) || !status || !n_pairs || !ws || n_labels < 0) return MSEG_EINVAL;
   if (radius < 1 || radius > NB_MAX_R) return MSEG_EINVAL;
   if (pair_cap < 0 || (pair_cap > 0 && !pairs) || pair_cap > (1ll << 40)) return MSEG_EINVAL;
   if (n_labels > 0 && !out) return MSEG_EINVAL;
@@ -341,23 +311,20 @@ extern "C" int mseg_cell_neighbors(const void* labels, int dtype, int T, int H, 
   const NbWs w = nb_carve(ws, T, n_labels, table_cap);
   int64_t items = entries > n_labels ? entries : n_labels;
   if (T > items) items = T;
-  hipLaunchKernelGGL(nb_init_kernel, dim3(nb_blocks(items)), dim3(NB_BLOCK), 0, st, w, entries, n_labels, out, status, T,
-                     n_pairs);
+  hipLaunchKernelGGL(nb_init_kernel, dim3(mseg_blocks(items, NB_BLOCK)), dim3(NB_BLOCK), 0, st, w, entries, n_labels, out,
+                     status, T, n_pairs);
   const size_t cells = (size_t)(NB_TH + radius + 1) * (size_t)(NB_TW + 2 * radius);
   const uint32_t cap = (uint32_t)table_cap;                         // 2^31 at most
-  if (dtype == MSEG_PIX_U16)
-    hipLaunchKernelGGL((nb_tile_kernel<uint16_t, uint16_t>), dim3((unsigned)tiles), dim3(NB_BLOCK),
-                       (cells * sizeof(uint16_t) + 15) / 16 * 16, st, (const uint16_t*)labels, H, W, tiles_x, tiles_y,
-                       label_off, radius, w, cap, (u64*)out, n_labels, status);
-  else
-    hipLaunchKernelGGL((nb_tile_kernel<int32_t, int32_t>), dim3((unsigned)tiles), dim3(NB_BLOCK),
-                       (cells * sizeof(int32_t) + 15) / 16 * 16, st, (const int32_t*)labels, H, W, tiles_x, tiles_y, label_off,
-                       radius, w, cap, (u64*)out, n_labels, status);
+  cell_dispatch(dtype, [&](auto l) {
+    typedef decltype(l) L;                                          // the tile in LDS holds the labels' own type
+    hipLaunchKernelGGL((nb_tile_kernel<L, L>), dim3((unsigned)tiles), dim3(NB_BLOCK), (cells * sizeof(L) + 15) / 16 * 16, st,
+                       (const L*)labels, H, W, tiles_x, tiles_y, label_off, radius, w, cap, (u64*)out, n_labels, status);
+  });
   int cap_shift = 0;
   while ((1ll << cap_shift) < table_cap) ++cap_shift;
-  hipLaunchKernelGGL(nb_table_kernel, dim3(nb_blocks(entries)), dim3(NB_BLOCK), 0, st, w, entries, cap_shift, label_off,
+  hipLaunchKernelGGL(nb_table_kernel, dim3(mseg_blocks(entries, NB_BLOCK)), dim3(NB_BLOCK), 0, st, w, entries, cap_shift, label_off,
                      (u64*)out, n_labels, pairs, pair_cap, (u64*)n_pairs);
-  hipLaunchKernelGGL(nb_finish_kernel, dim3(nb_blocks(n_labels)), dim3(NB_BLOCK), 0, st, w, n_labels, out);
+  hipLaunchKernelGGL(nb_finish_kernel, dim3(mseg_blocks(n_labels, NB_BLOCK)), dim3(NB_BLOCK), 0, st, w, n_labels, out);
   MSEG_LAUNCH_CHECK();
   return MSEG_OK;
 }

@@ -11,7 +11,7 @@
 //   os_bg_hist_kernel<.., 1>  uint16: the low-byte histograms of the chosen bins
 //   os_bg_low_kernel    one wave per (frame, channel): the values
 // Integers only, order-free integer adds: identical bytes from run to run.
-#include "common.h"
+#include "cell_common.h"
 
 #define OS_WAVE 64
 #define OS_MAXR 16
@@ -20,8 +20,6 @@
 #define OS_BG_SHARE 65536         // background pixels of one frame and channel a workgroup walks: 256 per thread
 
 namespace {
-
-inline size_t os_align(size_t v) { return (v + 255) / 256 * 256; }
 
 struct OsSel {                    // where a rank fell in the high-byte histogram
   int32_t bin;                    // the bin, -1: the rank is not in 0 .. m - 1 (or there is no pixel at all)
@@ -41,8 +39,8 @@ inline OsWs os_carve(void* ws, int T, int C, int R) {
   char* b = (char*)ws;
   OsWs w;
   w.hi = (uint32_t*)b;
-  w.low = (uint32_t*)(b + os_align(tc * OS_BINS * 4));
-  w.sel = (OsSel*)(b + os_align(tc * OS_BINS * 4) + os_align(tc * R * OS_BINS * 4));
+  w.low = (uint32_t*)(b + mseg_align256(tc * OS_BINS * 4));
+  w.sel = (OsSel*)(b + mseg_align256(tc * OS_BINS * 4) + mseg_align256(tc * R * OS_BINS * 4));
   return w;
 }
 
@@ -370,7 +368,7 @@ extern "C" size_t mseg_cell_order_stats_workspace_bytes(int T, int64_t n_labels,
   if (T <= 0 || n_labels < 0 || C < 1 || R < 1 || R > OS_MAXR) return 0;
   const size_t tc = (size_t)T * (size_t)C;
   if (tc > (1u << 20)) return 0;
-  return os_align(tc * OS_BINS * 4) + os_align(tc * R * OS_BINS * 4) + os_align(tc * R * sizeof(OsSel));
+  return mseg_align256(tc * OS_BINS * 4) + mseg_align256(tc * R * OS_BINS * 4) + mseg_align256(tc * R * sizeof(OsSel));
 }
 
 extern "C" int mseg_cell_order_stats(const void* labels, int label_dtype, int T, int H, int W, const int64_t* label_off,
@@ -378,11 +376,9 @@ extern "C" int mseg_cell_order_stats(const void* labels, int label_dtype, int T,
                                      int64_t chan_stride, int64_t row_stride, int64_t pix_stride, const int32_t* bbox, int R,
                                      const int64_t* ranks, const int64_t* bg_ranks, uint32_t* values, uint32_t* bg_values,
                                      int32_t* status, void* ws, size_t ws_bytes, void* stream) {
-  if (!labels || !label_off || !img || !bg_ranks || !bg_values || !status || !ws) return MSEG_EINVAL;
-  if (T <= 0 || H <= 0 || W <= 0 || n_labels < 0 || C < 1 || R < 1 || R > OS_MAXR) return MSEG_EINVAL;
-  if ((int64_t)H * W >= (1ll << 31) - 512) return MSEG_EINVAL;
-  if (label_dtype != MSEG_PIX_U16 && label_dtype != MSEG_PIX_I32) return MSEG_EINVAL;
-  if (img_dtype != MSEG_PIX_U8 && img_dtype != MSEG_PIX_U16) return MSEG_EINVAL;
+  if (!img || !bg_ranks || !bg_values || !status || !ws) return MSEG_EINVAL;
+  if (!cell_stack_ok(labels, label_off, label_dtype, T, H, W, 512) || !cell_image_ok(img_dtype)) return MSEG_EINVAL;
+  if (n_labels < 0 || C < 1 || R < 1 || R > OS_MAXR) return MSEG_EINVAL;
   if (n_labels > 0 && (!bbox || !ranks || !values)) return MSEG_EINVAL;
   const size_t need = mseg_cell_order_stats_workspace_bytes(T, n_labels, C, R);
   if (need == 0) return MSEG_EINVAL;
@@ -393,15 +389,10 @@ extern "C" int mseg_cell_order_stats(const void* labels, int label_dtype, int T,
   if (hipMemsetAsync(ws, 0, need, st) != hipSuccess) return MSEG_ELAUNCH;
   if (hipMemsetAsync(status, 0, sizeof(int32_t), st) != hipSuccess) return MSEG_ELAUNCH;
   const OsWs w = os_carve(ws, T, C, R);
-#define OS_GO(L, P)                                                                                                        \
-  os_launch<L, P>(st, labels, T, H, W, label_off, n_labels, img, C, frame_stride, chan_stride, row_stride, pix_stride, bbox, \
-                  R, ranks, bg_ranks, values, bg_values, status, w)
-  if (label_dtype == MSEG_PIX_U16) {
-    if (img_dtype == MSEG_PIX_U8) OS_GO(uint16_t, uint8_t); else OS_GO(uint16_t, uint16_t);
-  } else {
-    if (img_dtype == MSEG_PIX_U8) OS_GO(int32_t, uint8_t); else OS_GO(int32_t, uint16_t);
-  }
-#undef OS_GO
+  cell_dispatch(label_dtype, img_dtype, [&](auto l, auto p) {
+    os_launch<decltype(l), decltype(p)>(st, labels, T, H, W, label_off, n_labels, img, C, frame_stride, chan_stride, row_stride,
+                                        pix_stride, bbox, R, ranks, bg_ranks, values, bg_values, status, w);
+  });
   MSEG_LAUNCH_CHECK();
   return MSEG_OK;
 }

@@ -14,7 +14,7 @@
 //                   the tile and a ring of 1 in registers, D into LDS over the horizontal sums, the peak test on the tile;
 //                   per spot one atomic add on its cell's (or its frame's background) counter and one on the list cursor
 // Integers only, order-free integer adds; the list arrives in any order and is sorted by the caller.
-#include "common.h"
+#include "cell_common.h"
 
 #define SP_TH 32
 #define SP_TW 64
@@ -29,8 +29,6 @@
 #define SP_WS_BYTES 256
 
 namespace {
-
-typedef unsigned long long u64;
 
 inline size_t sp_align16(size_t v) { return (v + 15) / 16 * 16; }
 
@@ -165,10 +163,10 @@ __global__ void __launch_bounds__(SP_BLOCK) sp_tile_kernel(const L* __restrict__
         peak = peak && ((dy < 0 || (dy == 0 && dx < 0)) ? v > w : v >= w);
       }
     if (!peak) continue;
-    const int64_t l = (int64_t)lab[((int64_t)t * H + y) * W + x];
+    const int l = (int)lab[((int64_t)t * H + y) * W + x];
     if (l == 0) {
       atomicAdd(&bg_count[(int64_t)t * C + c], 1);
-    } else if (l >= 1 && l <= k_t) {
+    } else if (cell_id(l, k_t)) {
       const int64_t slot = loff[t] + l - 1;
       if (slot >= 0 && slot < n) atomicAdd(&cell_count[(int64_t)c * n + slot], 1);
     }
@@ -196,9 +194,10 @@ void sp_launch_s(hipStream_t st, unsigned tiles, const void* labels, int T, int 
                      cell_count, bg_count, spots, cap, n_found, status);
 }
 
-// W5: the type of the B_2s row sums at s = 5 (uint16 images: 64 bits); below that 32 bits always do
-template <typename L, typename P, typename W5, typename... A>
+// W5: the type of the B_2s row sums at s = 5 (uint16 images: 64 bits, 65535 * 4^10 >= 2^32); below that 32 bits always do
+template <typename L, typename P, typename... A>
 void sp_launch(int s, A... a) {
+  typedef typename std::conditional<sizeof(P) == 1, uint32_t, u64>::type W5;
   switch (s) {
     case 1: sp_launch_s<L, P, uint32_t, 1>(a...); break;
     case 2: sp_launch_s<L, P, uint32_t, 2>(a...); break;
@@ -221,11 +220,9 @@ extern "C" int mseg_cell_spots(const void* labels, int label_dtype, int T, int H
                                int64_t chan_stride, int64_t row_stride, int64_t pix_stride, int scale, int threshold,
                                int32_t* cell_count, int32_t* bg_count, MsegSpot* spots, int64_t spot_cap, int64_t* n_spots,
                                int32_t* status, void* ws, size_t ws_bytes, void* stream) {
-  if (!labels || !label_off || !img || !bg_count || !n_spots || !status || !ws) return MSEG_EINVAL;
-  if (T <= 0 || H <= 0 || W <= 0 || n_labels < 0 || C < 1) return MSEG_EINVAL;
-  if ((int64_t)H * W >= (1ll << 31) - 512) return MSEG_EINVAL;
-  if (label_dtype != MSEG_PIX_U16 && label_dtype != MSEG_PIX_I32) return MSEG_EINVAL;
-  if (img_dtype != MSEG_PIX_U8 && img_dtype != MSEG_PIX_U16) return MSEG_EINVAL;
+  if (!img || !bg_count || !n_spots || !status || !ws) return MSEG_EINVAL;
+  if (!cell_stack_ok(labels, label_off, label_dtype, T, H, W, 512) || !cell_image_ok(img_dtype)) return MSEG_EINVAL;
+  if (n_labels < 0 || C < 1) return MSEG_EINVAL;
   if (scale < 1 || scale > SP_MAXS || threshold < 1 || threshold > 65535) return MSEG_EINVAL;
   if (spot_cap < 0 || spot_cap > (1ll << 32) || (spot_cap > 0 && !spots)) return MSEG_EINVAL;
   if (n_labels > 0 && !cell_count) return MSEG_EINVAL;
@@ -246,16 +243,11 @@ extern "C" int mseg_cell_spots(const void* labels, int label_dtype, int T, int H
   hipLaunchKernelGGL(sp_init_kernel, dim3((unsigned)blocks), dim3(SP_BLOCK), 0, st, taps, scale, cell_count, n_cell, bg_count,
                      n_bg, (u64*)n_spots, status);
   const int64_t thr = (int64_t)threshold << (8 * scale);              // thr * 16^(2s)
-#define SP_GO(L, P, W5)                                                                                                     \
-  sp_launch<L, P, W5>(scale, st, (unsigned)tiles, labels, T, H, W, label_off, n_labels, img, C, frame_stride, chan_stride,    \
-                      row_stride, pix_stride, thr, (const uint32_t*)taps, tiles_x, tiles_y, cell_count, bg_count, spots,      \
-                      spot_cap, (u64*)n_spots, status)
-  if (label_dtype == MSEG_PIX_U16) {
-    if (img_dtype == MSEG_PIX_U8) SP_GO(uint16_t, uint8_t, uint32_t); else SP_GO(uint16_t, uint16_t, u64);   // 65535 * 4^10 >= 2^32
-  } else {
-    if (img_dtype == MSEG_PIX_U8) SP_GO(int32_t, uint8_t, uint32_t); else SP_GO(int32_t, uint16_t, u64);
-  }
-#undef SP_GO
+  cell_dispatch(label_dtype, img_dtype, [&](auto l, auto p) {
+    sp_launch<decltype(l), decltype(p)>(scale, st, (unsigned)tiles, labels, T, H, W, label_off, n_labels, img, C, frame_stride,
+                                        chan_stride, row_stride, pix_stride, thr, (const uint32_t*)taps, tiles_x, tiles_y,
+                                        cell_count, bg_count, spots, spot_cap, (u64*)n_spots, status);
+  });
   MSEG_LAUNCH_CHECK();
   return MSEG_OK;
 }

@@ -195,6 +195,26 @@ def _channel_groups(channels):
     return groups
 
 
+def _offsets_to_device(off, dev):
+    """the host table of label offsets [T + 1] as an int64 device tensor"""
+    return torch.from_numpy(np.ascontiguousarray(off, np.int64)).to(dev)
+
+
+def _workspace(nbytes, dev, refused):
+    """the device workspace a ``*_workspace_bytes`` call asked for; 0 bytes: the library takes no such arguments"""
+    if nbytes == 0:
+        raise ValueError(refused)
+    return torch.empty(nbytes, dtype=torch.uint8, device=dev)
+
+
+def _channel_run(image, group):
+    """the image arguments of a C call (address, MSEG_PIX_*, channels, frame / channel / row / pixel stride) for one run
+    (first, step, count) of ``_channel_groups`` in the memory of an ``_image_to_device`` tuple"""
+    _, base, ipix, _, (fs, cs0, rs, ps) = image
+    first, step, count = group
+    return base + first * cs0 * (1 if ipix == _lib.PIX_U8 else 2), ipix, count, fs, step * cs0, rs, ps
+
+
 def measure_raw(lab, pix, off, image=None, channels=()):
     """The integer sums of ``mseg_cell_measure`` as host arrays.  lab: device labels [T, H, W]; off: int64 [T + 1] host
     table; image: the tuple of ``_image_to_device``.  -> dict: shape uint64 [6, n], bbox int32 [n, 4], ch_sums uint64
@@ -203,23 +223,19 @@ def measure_raw(lab, pix, off, image=None, channels=()):
     dev = lab.device
     T, H, W = (int(v) for v in lab.shape)
     n = int(off[-1])
-    off_d = torch.from_numpy(np.ascontiguousarray(off, np.int64)).to(dev)
+    off_d = _offsets_to_device(off, dev)
     shape = torch.zeros((6, max(n, 1)), dtype=torch.int64, device=dev)
     bbox = torch.zeros((max(n, 1), 4), dtype=torch.int32, device=dev)
     out = {"ch_sums": [], "ch_minmax": [], "bg_sums": [], "bg_minmax": []}
     calls = _channel_groups(list(channels)) if image is not None and len(channels) else [None]
     for g in calls:
-        if g is None:
-            ptr, ipix, Cg, fs, cs, rs, ps = None, 0, 0, 0, 0, 0, 0
-        else:
-            _, base, ipix, _, (fs, cs0, rs, ps) = image
-            first, step, Cg = g
-            ptr, cs = base + first * cs0 * (1 if ipix == _lib.PIX_U8 else 2), step * cs0
+        img_args = (None, 0, 0, 0, 0, 0, 0) if g is None else _channel_run(image, g)
+        Cg = img_args[2]
         chs = torch.zeros((2, max(Cg, 1), max(n, 1)), dtype=torch.int64, device=dev)
         chm = torch.zeros((2, max(Cg, 1), max(n, 1)), dtype=torch.int32, device=dev)
         bgs = torch.zeros((3, T, max(Cg, 1)), dtype=torch.int64, device=dev)
         bgm = torch.zeros((2, T, max(Cg, 1)), dtype=torch.int32, device=dev)
-        _lib.check(lib.mseg_cell_measure(lab.data_ptr(), pix, T, H, W, off_d.data_ptr(), n, ptr, ipix, Cg, fs, cs, rs, ps,
+        _lib.check(lib.mseg_cell_measure(lab.data_ptr(), pix, T, H, W, off_d.data_ptr(), n, *img_args,
                                          shape.data_ptr(), bbox.data_ptr(), chs.data_ptr(), chm.data_ptr(),
                                          bgs.data_ptr(), bgm.data_ptr(), _stream(dev)), "cell_measure")
         if Cg:
@@ -249,13 +265,11 @@ def hull_raw(lab, pix, off, bbox):
     n_rows = int(row_off[-1])
     if n == 0:
         return np.zeros((10, 0), np.int64)
-    off_d = torch.from_numpy(np.ascontiguousarray(off, np.int64)).to(dev)
+    off_d = _offsets_to_device(off, dev)
     bbox_d, row_d = torch.from_numpy(bbox).to(dev), torch.from_numpy(row_off).to(dev)
     out = torch.zeros(10 * n + 1, dtype=torch.int64, device=dev)      # the last element holds the status word: one download
-    nbytes = lib.mseg_cell_hull_workspace_bytes(n, n_rows)
-    if nbytes == 0:
-        raise ValueError(f"mseg_cell_hull: no workspace for {n} cells with {n_rows} rows")
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws = _workspace(lib.mseg_cell_hull_workspace_bytes(n, n_rows), dev,
+                    f"mseg_cell_hull: no workspace for {n} cells with {n_rows} rows")
     _lib.check(lib.mseg_cell_hull(lab.data_ptr(), pix, T, H, W, off_d.data_ptr(), n, bbox_d.data_ptr(), row_d.data_ptr(),
                                   n_rows, out.data_ptr(), out.data_ptr() + 80 * n, ws.data_ptr(), ws.numel(), _stream(dev)),
                "cell_hull")
@@ -282,13 +296,11 @@ def midline_raw(lab, pix, off, bbox, skeleton=False):
         ints = np.zeros((12, 0), np.int64)
         return (ints, np.zeros((T, H, W), np.uint8)) if skeleton else ints
     skel = torch.empty((T, H, W), dtype=torch.uint8, device=dev) if skeleton else None
-    off_d = torch.from_numpy(np.ascontiguousarray(off, np.int64)).to(dev)
+    off_d = _offsets_to_device(off, dev)
     bbox_d, word_d = torch.from_numpy(bbox).to(dev), torch.from_numpy(word_off).to(dev)
     out = torch.zeros(12 * n + 1, dtype=torch.int64, device=dev)      # the last element holds the status word: one download
-    nbytes = lib.mseg_cell_midline_workspace_bytes(n, n_words)
-    if nbytes == 0:
-        raise ValueError(f"mseg_cell_midline: no workspace for {n} cells with {n_words} words")
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws = _workspace(lib.mseg_cell_midline_workspace_bytes(n, n_words), dev,
+                    f"mseg_cell_midline: no workspace for {n} cells with {n_words} words")
     _lib.check(lib.mseg_cell_midline(lab.data_ptr(), pix, T, H, W, off_d.data_ptr(), n, bbox_d.data_ptr(), word_d.data_ptr(),
                                      n_words, out.data_ptr(), skel.data_ptr() if skeleton else None, out.data_ptr() + 96 * n,
                                      ws.data_ptr(), ws.numel(), _stream(dev)), "cell_midline")
@@ -366,22 +378,19 @@ def order_stats_raw(lab, pix, off, image, channels, bbox, ranks, bg_ranks):
         raise ValueError("order statistics are taken of an image's channels: none given")
     if bg_ranks.shape != (R, T) or ranks.shape != (R, n):
         raise ValueError(f"ranks [{R}, {n}] and bg_ranks [{R}, {T}] expected, got {ranks.shape} and {bg_ranks.shape}")
-    off_d = torch.from_numpy(np.ascontiguousarray(off, np.int64)).to(dev)
+    off_d = _offsets_to_device(off, dev)
     bbox_d = torch.from_numpy(np.ascontiguousarray(bbox, np.int32).reshape(n, 4)).to(dev) if n else None
     ranks_d = torch.from_numpy(ranks).to(dev) if n else None
     bg_ranks_d = torch.from_numpy(bg_ranks).to(dev)
-    _, base, ipix, _, (fs, cs0, rs, ps) = image
     vals, bgs = [], []
-    for first, step, Cg in _channel_groups(list(channels)):
-        nbytes = lib.mseg_cell_order_stats_workspace_bytes(T, n, Cg, R)
-        if nbytes == 0:
-            raise ValueError(f"mseg_cell_order_stats: no workspace for T = {T}, {Cg} channels, {R} ranks")
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    for group in _channel_groups(list(channels)):
+        Cg = group[2]
+        ws = _workspace(lib.mseg_cell_order_stats_workspace_bytes(T, n, Cg, R), dev,
+                        f"mseg_cell_order_stats: no workspace for T = {T}, {Cg} channels, {R} ranks")
         out = torch.zeros(R * Cg * n + R * T * Cg + 1, dtype=torch.int32, device=dev)      # values, bg_values, status: one download
         v_ptr, b_ptr = out.data_ptr(), out.data_ptr() + 4 * R * Cg * n
-        _lib.check(lib.mseg_cell_order_stats(lab.data_ptr(), pix, T, H, W, off_d.data_ptr(), n,
-                                             base + first * cs0 * (1 if ipix == _lib.PIX_U8 else 2), ipix, Cg, fs, step * cs0,
-                                             rs, ps, bbox_d.data_ptr() if n else None, R, ranks_d.data_ptr() if n else None,
+        _lib.check(lib.mseg_cell_order_stats(lab.data_ptr(), pix, T, H, W, off_d.data_ptr(), n, *_channel_run(image, group),
+                                             bbox_d.data_ptr() if n else None, R, ranks_d.data_ptr() if n else None,
                                              bg_ranks_d.data_ptr(), v_ptr if n else None, b_ptr, b_ptr + 4 * R * T * Cg,
                                              ws.data_ptr(), ws.numel(), _stream(dev)), "cell_order_stats")
         host = out.cpu().numpy().view(np.uint32)
@@ -414,12 +423,10 @@ def drift_raw(lab, pix, off, max_drift):
     T, H, W = (int(v) for v in lab.shape)
     R = int(max_drift)
     side = 2 * R + 1
-    off_d = torch.from_numpy(np.ascontiguousarray(off, np.int64)).to(dev)
+    off_d = _offsets_to_device(off, dev)
     scores = torch.zeros((max(T - 1, 1), side, side), dtype=torch.int32, device=dev)
-    nbytes = lib.mseg_stack_drift_workspace_bytes(T, H, W)
-    if nbytes == 0:
-        raise ValueError(f"mseg_stack_drift: no workspace for a {T} x {H} x {W} stack")
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws = _workspace(lib.mseg_stack_drift_workspace_bytes(T, H, W), dev,
+                    f"mseg_stack_drift: no workspace for a {T} x {H} x {W} stack")
     _lib.check(lib.mseg_stack_drift(lab.data_ptr(), pix, T, H, W, off_d.data_ptr(), R, scores.data_ptr(), ws.data_ptr(),
                                     ws.numel(), _stream(dev)), "stack_drift")
     return scores.cpu().numpy().view(np.uint32)[:T - 1]
@@ -470,13 +477,11 @@ def flow_raw(lab, pix, off, base, radius, tile):
     if base.shape != (T, 2):
         raise ValueError(f"base: int32 [{T}, 2] expected, got {base.shape}")
     ty, tx, side = -(-H // B), -(-W // B), 2 * r + 1
-    off_d = torch.from_numpy(np.ascontiguousarray(off, np.int64)).to(dev)
+    off_d = _offsets_to_device(off, dev)
     base_d = torch.from_numpy(base).to(dev)
     scores = torch.zeros((max(T - 1, 1), ty, tx, side, side), dtype=torch.int32, device=dev)
-    nbytes = lib.mseg_stack_flow_workspace_bytes(T, H, W)
-    if nbytes == 0:
-        raise ValueError(f"mseg_stack_flow: no workspace for a {T} x {H} x {W} stack")
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws = _workspace(lib.mseg_stack_flow_workspace_bytes(T, H, W), dev,
+                    f"mseg_stack_flow: no workspace for a {T} x {H} x {W} stack")
     _lib.check(lib.mseg_stack_flow(lab.data_ptr(), pix, T, H, W, off_d.data_ptr(), B, r, base_d.data_ptr(),
                                    scores.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)), "stack_flow")
     return scores.cpu().numpy().view(np.uint32)[:T - 1]
@@ -513,14 +518,12 @@ def _links_call(lab, pix, off, cap, shift=None, tile=None):
     dev = lab.device
     T, H, W = (int(v) for v in lab.shape)
     n = int(off[-1])
-    off_d = torch.from_numpy(np.ascontiguousarray(off, np.int64)).to(dev)
+    off_d = _offsets_to_device(off, dev)
     pred = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
     ovl = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
     status = torch.zeros(T, dtype=torch.int32, device=dev)
-    nbytes = lib.mseg_cell_links_workspace_bytes(T, n, cap)
-    if nbytes == 0:
-        raise ValueError(f"mseg_cell_links: no workspace for T = {T}, {n} cells, table {cap}")
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws = _workspace(lib.mseg_cell_links_workspace_bytes(T, n, cap), dev,
+                    f"mseg_cell_links: no workspace for T = {T}, {n} cells, table {cap}")
     if tile is not None:
         field_d = torch.from_numpy(np.ascontiguousarray(shift, np.int32)).to(dev)
         _lib.check(lib.mseg_cell_links_field(lab.data_ptr(), pix, T, H, W, off_d.data_ptr(), n, cap, int(tile),
@@ -596,11 +599,9 @@ def _neighbors_call(lab, pix, off, radius, cap, pair_cap):
     dev = lab.device
     T, H, W = (int(v) for v in lab.shape)
     n = int(off[-1])
-    off_d = torch.from_numpy(np.array(off, np.int64)).to(dev)
-    nbytes = lib.mseg_cell_neighbors_workspace_bytes(T, n, cap)
-    if nbytes == 0:
-        raise ValueError(f"mseg_cell_neighbors: no workspace for T = {T}, {n} cells, table {cap}")
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    off_d = _offsets_to_device(off, dev)
+    ws = _workspace(lib.mseg_cell_neighbors_workspace_bytes(T, n, cap), dev,
+                    f"mseg_cell_neighbors: no workspace for T = {T}, {n} cells, table {cap}")
     out = torch.zeros((9, max(n, 1)), dtype=torch.int64, device=dev)
     tail = torch.zeros(1 + (T + 1) // 2, dtype=torch.int64, device=dev)      # n_pairs, then the T status words: one download
     while True:
@@ -721,23 +722,20 @@ def spots_raw(lab, pix, off, image, channels, thr, scale, spot_cap=None):
     if check_spots(thr, scale) is None:
         raise ValueError("spots_raw: a threshold is needed")
     thr, scale = check_spots(thr, scale)
-    off_d = torch.from_numpy(np.ascontiguousarray(off, np.int64)).to(dev)
-    _, base, ipix, _, (fs, cs0, rs, ps) = image
+    off_d = _offsets_to_device(off, dev)
     counts, bgs, recs, first_ci = [], [], [], 0
-    for first, step, Cg in _channel_groups(list(channels)):
-        nbytes = lib.mseg_cell_spots_workspace_bytes(T, n, Cg)
-        if nbytes == 0:
-            raise ValueError(f"mseg_cell_spots: no workspace for T = {T}, {n} cells, {Cg} channels")
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    for group in _channel_groups(list(channels)):
+        Cg = group[2]
+        ws = _workspace(lib.mseg_cell_spots_workspace_bytes(T, n, Cg), dev,
+                        f"mseg_cell_spots: no workspace for T = {T}, {n} cells, {Cg} channels")
         top = spot_bound(T, H, W, Cg)
         cap = min(top, (4 * n + 1024 * T) * Cg) if spot_cap is None else max(int(spot_cap), 0)
         while True:
             tail = torch.zeros(2, dtype=torch.int64, device=dev)                      # n_spots, then the status word
             ints = torch.zeros(Cg * n + T * Cg, dtype=torch.int32, device=dev)       # cell_count, then bg_count
             lst = torch.zeros((max(cap, 1), 4), dtype=torch.int64, device=dev)       # 32 bytes per record
-            _lib.check(lib.mseg_cell_spots(lab.data_ptr(), pix, T, H, W, off_d.data_ptr(), n,
-                                           base + first * cs0 * (1 if ipix == _lib.PIX_U8 else 2), ipix, Cg, fs, step * cs0, rs,
-                                           ps, scale, thr, ints.data_ptr() if n else None, ints.data_ptr() + 4 * Cg * n,
+            _lib.check(lib.mseg_cell_spots(lab.data_ptr(), pix, T, H, W, off_d.data_ptr(), n, *_channel_run(image, group),
+                                           scale, thr, ints.data_ptr() if n else None, ints.data_ptr() + 4 * Cg * n,
                                            lst.data_ptr() if cap else None, cap, tail.data_ptr(), tail.data_ptr() + 8,
                                            ws.data_ptr(), ws.numel(), _stream(dev)), "cell_spots")
             end = tail.cpu().numpy()

@@ -17,6 +17,7 @@ pytestmark = pytest.mark.gpu
 GUARD = 64
 SENT64, SENT32 = -0x0123456789ABCDEF, 0x5A5A5A5A
 PIX = {np.dtype(np.uint8): 0, np.dtype(np.uint16): 1, np.dtype(np.int32): 2}
+EINVAL, EWORKSPACE = -1, -3
 
 
 @pytest.fixture(autouse=True)
@@ -402,6 +403,97 @@ def test_links_random_case_and_table_overflow():
                               for t, k in enumerate(np.diff(off))])
     assert np.array_equal(df["pred_label"].to_numpy(), want_pred[present])
     assert np.array_equal(df["overlap"].to_numpy(), want_ovl[present])
+
+
+@pytest.mark.parametrize("label_dtype", [np.uint16, np.int32])
+@pytest.mark.parametrize("shape", [(5, 63), (5, 65), (70, 131)])
+def test_links_on_frames_that_are_no_multiple_of_eight_pixels(shape, label_dtype):
+    """H * W = 315, 325, 9170: the last lane of every frame takes the loader's scalar tail, and with uint16 labels every
+    second frame starts at an address that is no multiple of 16 bytes.  The plain call against the restatement, and byte for
+    byte against the shifted and the field call under all-zero shifts."""
+    import drift_ref as dref
+    from test_gpu_drift import c_links_shifted, random_labels
+    from test_gpu_flow import c_links_field
+    H, W = shape
+    lab64, off = random_labels(H, W)
+    T = lab64.shape[0]
+    lab, off = lab64.astype(label_dtype), np.array(off)       # copies: the sources are read-only
+    assert T == 4 and (H * W) % 8 != 0
+    zero = np.zeros((T, 2), np.int32)
+    field = np.zeros((T, -(-H // 64), -(-W // 64), 2), np.int32)
+    want_pred, want_ovl = dref.links_shifted(lab64, off, zero)
+    assert want_ovl.any()
+    clean = 1 << (H * W).bit_length()                         # more entries than pixels: cannot fill up
+    for cap in (64, clean):
+        pred, ovl, status = c_links(lab, off, cap)
+        moved = [c_links_shifted(lab, off, cap, zero), c_links_field(lab, off, cap, field, 64)]
+        assert status[0] == 0 and (cap == 64 or not status.any())
+        for other in moved:
+            assert np.array_equal(other[2] != 0, status != 0), cap
+        for t in np.nonzero(status == 0)[0]:
+            s = slice(int(off[t]), int(off[t + 1]))
+            assert np.array_equal(pred[s], want_pred[s]) and np.array_equal(ovl[s], want_ovl[s]), (cap, t)
+            for other in moved:
+                assert pred[s].tobytes() == other[0][s].tobytes() and ovl[s].tobytes() == other[1][s].tobytes(), (cap, t)
+
+
+def c_cells_refused(entry, lab, off, dtype_code=None, dims=None, n=None, cap=1024, tile=64, null_shift=False, short=0):
+    """One call of ``entry`` (measure, links, links_shifted, links_field) that must be refused: every output and the
+    workspace are guarded and pre-filled.  The overrides replace single arguments of an otherwise valid call.
+    -> (return code, True if nothing was written)"""
+    from microbeseg_amd import _lib
+    lib = _lib.load()
+    T, H, W = lab.shape
+    n_real = int(off[-1])
+    lab_d, off_d = _dev(lab), torch.from_numpy(np.array(off, np.int64)).cuda()      # a copy: the source is read-only
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    head = (lab_d.data_ptr(), PIX[lab.dtype] if dtype_code is None else dtype_code, *(dims or (T, H, W)), off_d.data_ptr(),
+            n_real if n is None else n)
+    if entry == "measure":
+        img = _dev(np.random.default_rng(1).integers(0, 65536, (T, 1, H, W)).astype(np.uint16))
+        bufs = [Guarded((6, n_real), torch.int64), Guarded((n_real, 4), torch.int32), Guarded((2, 1, n_real), torch.int64),
+                Guarded((2, 1, n_real), torch.int32), Guarded((3, T, 1), torch.int64), Guarded((2, T, 1), torch.int32)]
+        code = lib.mseg_cell_measure(*head, img.data_ptr(), PIX[np.dtype(np.uint16)], 1, H * W, H * W, W, 1,
+                                     *(b.ptr for b in bufs), stream)
+    else:
+        bufs = [Guarded((n_real,), torch.int32), Guarded((n_real,), torch.int32), Guarded((T,), torch.int32)]
+        nbytes = lib.mseg_cell_links_workspace_bytes(T, n_real, 1024)
+        assert nbytes > 0
+        ws = Guarded((nbytes // 4,), torch.int32)
+        bufs.append(ws)
+        tail = (*(b.ptr for b in bufs[:3]), ws.ptr, nbytes - short, stream)
+        if entry == "links":
+            code = lib.mseg_cell_links(*head, cap, *tail)
+        elif entry == "links_shifted":
+            shift = torch.zeros((T, 2), dtype=torch.int32, device="cuda")
+            code = lib.mseg_cell_links_shifted(*head, cap, None if null_shift else shift.data_ptr(), *tail)
+        else:
+            field = torch.zeros((T, -(-H // 64), -(-W // 64), 2), dtype=torch.int32, device="cuda")
+            code = lib.mseg_cell_links_field(*head, cap, tile, field.data_ptr(), *tail)
+    torch.cuda.synchronize()
+    return code, all(b.untouched() for b in bufs)
+
+
+@pytest.mark.parametrize("entry", ["measure", "links", "links_shifted", "links_field"])
+def test_argument_errors_touch_nothing(entry):
+    """a refused call writes nothing: neither an output, nor a status word, nor the workspace (so no memset and no kernel ran)"""
+    from test_gpu_drift import random_labels
+    lab64, off = random_labels(5, 65)
+    lab = lab64.astype(np.uint16)
+    T, H, W = lab.shape
+    bad = [dict(dtype_code=0), dict(dtype_code=3), dict(n=-1)]
+    bad += [dict(dims=d) for d in ((0, H, W), (T, 0, W), (T, H, 0), (-1, H, W), (T, -5, W), (T, H, -65))]
+    if entry != "measure":
+        bad += [dict(cap=96), dict(cap=32)]
+    if entry == "links_field":
+        bad.append(dict(tile=32))
+    if entry == "links_shifted":
+        bad.append(dict(null_shift=True))
+    assert c_cells_refused(entry, lab, off) == (0, False)       # the call the bad ones are made from is a good one
+    for kw in bad:
+        assert c_cells_refused(entry, lab, off, **kw) == (EINVAL, True), kw
+    if entry != "measure":
+        assert c_cells_refused(entry, lab, off, short=1) == (EWORKSPACE, True)
 
 
 # ---- end to end ----------------------------------------------------------------------------------------------------------------
