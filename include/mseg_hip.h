@@ -617,6 +617,23 @@ int mseg_cell_links_field(const void* labels, int dtype, int T, int H, int W, co
                           int64_t table_cap, int tile, const int32_t* field, int32_t* pred, int32_t* overlap,
                           int32_t* status, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- links across missed frames (csrc/cells.hip) — an extension -------------------------------------------
+ * mseg_cell_links_gap: mseg_cell_links (same outputs, workspace, pair table, status word per frame t, redo rule and tie
+ *   rule) against frame t - gap instead of frame t - 1, 1 <= gap <= 5, and between flagged cells only.  want, open: uint8
+ *   [n_labels] on the device in label_off order; want[slot] != 0: the cell of frame t takes part, open[slot] != 0: the cell
+ *   of frame t - gap may be found.  Pixel (y, x) of frame t pairs with (y - dy, x - dx) of frame t - gap, or with nothing
+ *   where that lies outside the frame: shift == NULL and tile == 0: (dy, dx) = (0, 0); tile == 0 with shift: int32 [T][2],
+ *   one (dy, dx) per frame t; tile one of 64, 128, 256 with shift: int32 [T][ty][tx][2] in the layout of
+ *   mseg_cell_links_field.  The motion is the caller's, ALREADY COMPOSED over the gap; any int32 is legal.  pred[slot] names
+ *   a label of frame t - gap; pred / overlap are 0 for cells with want == 0, for frames t < gap, and everywhere when
+ *   gap >= T (MSEG_OK).  Ids that are no cell of their frame index no flag.  gap == 1 with all flags set: the outputs of
+ *   mseg_cell_links / _shifted / _field, byte for byte.  MSEG_EINVAL also for a gap outside 1 .. 5, a tile without a shift
+ *   and a tile not listed; nothing is written then.                                                                        */
+int mseg_cell_links_gap(const void* labels, int dtype, int T, int H, int W, const int64_t* label_off, int64_t n_labels,
+                        int64_t table_cap, int gap, int tile, const int32_t* shift, const uint8_t* want,
+                        const uint8_t* open, int32_t* pred, int32_t* overlap, int32_t* status, void* ws, size_t ws_bytes,
+                        void* stream);
+
 /* ---- per-cell outline measures (csrc/hull.hip) — an extension --------------------------------------------
  * labels, dtype and label_off as for mseg_cell_links.  A cell is the union of the closed unit squares of its pixels: pixel
  * (y, x) is the square with the corners (y, x) .. (y + 1, x + 1), so corners are integer points in 0..H x 0..W.  A cell may

@@ -12,6 +12,7 @@ the GUI's Export button (inference/result_export.py) for the segmented channel o
 ``--scale S`` predicts every frame at S times its resolution and segments at its own (inference/resample.py);
 ``--drift [R]`` with ``--cells``: cells are linked under the stage drift found within +-R pixels (inference/cells.py);
 ``--flow [r] [--flow_tile B]`` with ``--cells --drift``: cells are linked under one shift per B px tile, within +-r pixels of the drift;
+``--gap [G]`` with ``--cells``: a cell missed in up to G consecutive frames keeps its track (inference/cells.py);
 ``--hull`` with ``--cells``: perimeter, convex hull and Feret length / width / angle of every cell (inference/cells.py);
 ``--midline`` with ``--cells``: the thinned midline of every cell: its length, for bent and filamentous cells (inference/cells.py);
 ``--percentiles [P ...]`` with ``--cells``: percentiles (default 50, the median) of every cell's pixel values and of the background;
@@ -90,6 +91,11 @@ class Parser(argparse.ArgumentParser):
                 self.error('--flow needs --drift (the tiles search around the stage drift of every frame pair)')
             if not 0 <= ns.flow <= 32:
                 self.error(f'--flow: a search radius of 0 .. 32 pixels expected, got {ns.flow}')
+        if ns.gap is not None:
+            if not ns.cells:
+                self.error('--gap needs --cells (it changes how the cell table links frames)')
+            if not 1 <= ns.gap <= 4:
+                self.error(f'--gap: 1 .. 4 missed frames expected, got {ns.gap}')
         if ns.drift is not None:
             if not ns.cells:
                 self.error('--drift needs --cells (it changes how the cell table links frames)')
@@ -182,7 +188,8 @@ def build_parser():
                              'centroid, bounding box, axis lengths, orientation, the intensity of the measured channels '
                              '(mean, std, min, max, sum, background mean) and pred_label / overlap / track_id / '
                              'parent_track.  Tracks come from OVERLAP linking (a cell follows the cell of the previous '
-                             'frame it shares the most pixels with): there is no motion model and no gap closing')
+                             'frame it shares the most pixels with): there is no motion model, and no gap closing unless '
+                             '--gap is given')
     parser.add_argument('--measure_channels', default=None, nargs='+', type=int,
                         help='[extension] with --cells: channels of the source image to measure (default: the segmented '
                              'channel; images without a channel axis have channel 0).  uint8 / uint16 images only: other '
@@ -202,9 +209,17 @@ def build_parser():
                              'under which it overlaps the previous mask most, found on the device; cells are linked under '
                              'that field, and the table gains flow_y / flow_x (the shift of the cell\'s tile against the '
                              'previous frame, drift included).  One shift per tile: no smoothing or interpolation of the '
-                             'field, no rotation, no per-cell search, no gap closing')
+                             'field, no rotation, no per-cell search; gaps are closed by --gap, not by the field')
     parser.add_argument('--flow_tile', default=64, type=int, choices=[64, 128, 256],
                         help='[extension] with --flow: the tile edge in pixels (default 64)')
+    parser.add_argument('--gap', nargs='?', const=1, default=None, type=int, metavar='G',
+                        help='[extension] with --cells: close gaps in the tracks.  A cell that the segmentation missed in up '
+                             'to G consecutive frames (default G = 1, 1 <= G <= 4) is linked to the cell that ended 2 .. G + 1 '
+                             'frames before it and shares the most pixels with it, under the --drift / --flow shifts summed '
+                             'over the gap (for --flow per tile index: an approximation), if they share at least '
+                             '--min_overlap pixels; its track goes on, and the table gains pred_gap: the number of frames '
+                             'back to the cell pred_label names (1 = an ordinary link).  Overlap only: no motion model, no '
+                             'per-cell search, no rows for the missed frames')
     parser.add_argument('--hull', default=False, action='store_true',
                         help='[extension] with --cells: add the measures of every cell\'s pixel outline: perimeter (exposed '
                              'pixel edges), convex_area and solidity, feret_max / feret_min (largest and smallest caliper: '
@@ -287,6 +302,7 @@ def main():
     worker.drift = args.drift
     worker.flow = args.flow
     worker.flow_tile = args.flow_tile
+    worker.gap = args.gap
     worker.hull = args.hull
     worker.midline = args.midline
     worker.percentiles = tuple(args.percentiles) if args.percentiles else None
@@ -300,6 +316,8 @@ def main():
     if args.flow is not None:
         print(f'Cell table: linking under a displacement field of {args.flow_tile} px tiles, each searched within '
               f'+-{args.flow} px of the stage drift')
+    if args.gap is not None:
+        print(f'Cell table: closing gaps of up to {args.gap} missed frame(s) in the tracks')
     if args.hull:
         print('Cell table: with the outline measures (perimeter, convex hull, Feret length / width / angle)')
     if args.midline:

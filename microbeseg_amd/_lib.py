@@ -189,6 +189,7 @@ SIGNATURES = {
     "mseg_stack_flow_workspace_bytes": (_SZ, [_I, _I, _I]),
     "mseg_stack_flow": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _P, _P, _P, _SZ, _P]),
     "mseg_cell_links_field": (_I, [_P, _I, _I, _I, _I, _P, C.c_int64, C.c_int64, _I, _P, _P, _P, _P, _P, _SZ, _P]),
+    "mseg_cell_links_gap": (_I, [_P, _I, _I, _I, _I, _P, C.c_int64, C.c_int64, _I, _I, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
     "mseg_cell_hull_workspace_bytes": (_SZ, [C.c_int64, C.c_int64]),
     "mseg_cell_hull": (_I, [_P, _I, _I, _I, _I, _P, C.c_int64, _P, _P, C.c_int64, _P, _P, _P, _SZ, _P]),
     "mseg_cell_midline_workspace_bytes": (_SZ, [C.c_int64, C.c_int64]),

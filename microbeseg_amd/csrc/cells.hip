@@ -7,6 +7,7 @@
 //   mseg_cell_links    per cell of frame t the label of frame t - 1 that shares the most pixels with it
 //   mseg_cell_links_shifted  the same with frame t - 1 moved by a per-pair integer shift (drift compensation, §6o)
 //   mseg_cell_links_field    the same with one integer shift per tile of frame t (tile-wise displacement field, §6v)
+//   mseg_cell_links_gap      the same against frame t - gap, between flagged cells only (gap closing, §6w)
 // Everything is integer arithmetic with order-free 64-bit atomics: bit-identical from run to run.
 #include "cell_common.h"
 
@@ -352,6 +353,72 @@ __global__ void __launch_bounds__(CM_BLOCK) cl_pairs_shifted_kernel(const L* __r
   cl_fold8(l, m, loff, t, keys, cnt, cap, status);
 }
 
+// The pairs across a gap (§6w): pixel (y, x) of frame t pairs with (y - dy, x - dx) of frame t - gap, for the cells of frame t
+// flagged in want and the cells of frame t - gap flagged in open only (bytes in label_off order).  The lane layout of the
+// shifted kernel, 8 pixels of one row; shift == nullptr: no motion, else one (dy, dx) per frame or (FIELD) per tile of frame t,
+// composed over the gap by the caller.  The wanted cells are few: a lane none of whose pixels belongs to one returns
+// before it touches frame t - gap, and only wanted pixels load their source.  A flag is read where a run of one id starts, and
+// only for an id that cell_id let pass: 1 .. K of its frame, so the index stays inside the frame's part of the array.  The
+// table of frame t keeps index t - 1: those of the frames below gap stay empty.
+template <typename L, bool FIELD>
+__global__ void __launch_bounds__(CM_BLOCK) cl_pairs_gap_kernel(const L* __restrict__ lab, int T, int H, int W,
+                                                                const int64_t* __restrict__ loff, int gap,
+                                                                const int32_t* __restrict__ shift, int tile,
+                                                                const uint8_t* __restrict__ want,
+                                                                const uint8_t* __restrict__ open, u64* __restrict__ keys,
+                                                                uint32_t* __restrict__ cnt, uint32_t cap,
+                                                                int32_t* __restrict__ status) {
+  const int64_t per_row = ((int64_t)W + CM_PPL - 1) / CM_PPL, groups = (int64_t)H * per_row;
+  const int64_t g = (int64_t)blockIdx.x * CM_BLOCK + threadIdx.x;
+  if (g >= (int64_t)(T - gap) * groups) return;
+  const int t = (int)(g / groups) + gap, ts = t - gap;
+  const int64_t in_frame = g - (int64_t)ts * groups;
+  const int y = (int)(in_frame / per_row);
+  const int x0 = (int)(in_frame - (int64_t)y * per_row) * CM_PPL;
+  const int64_t Kl = loff[t + 1] - loff[t], Km = loff[ts + 1] - loff[ts];
+  const uint8_t* wt = want + loff[t];
+  const uint8_t* os = open + loff[ts];
+  int l[CM_PPL], m[CM_PPL];
+  cell_load8<L>(lab + ((int64_t)t * H + y) * W, x0, W, l);               // positions past the row's end read as 0
+  int run = 0;
+  bool flag = false, any = false;
+#pragma unroll
+  for (int k = 0; k < CM_PPL; ++k) {
+    const int v = cell_id(l[k], Kl);
+    if (v != run) { run = v; flag = v && wt[v - 1]; }
+    l[k] = flag ? v : 0;
+    any |= flag;
+  }
+  if (!any) return;
+  int64_t ys = y, xs0 = x0;
+  if (shift) {
+    int64_t at = t;
+    if (FIELD) at = ((int64_t)t * ((H + tile - 1) / tile) + y / tile) * ((W + tile - 1) / tile) + x0 / tile;
+    ys -= shift[2 * at];
+    xs0 -= shift[2 * at + 1];
+  }
+  if (ys < 0 || ys >= H || xs0 + CM_PPL <= 0 || xs0 >= W) return;        // no pixel of this lane has a source
+  const L* pm = lab + ((int64_t)ts * H + ys) * W;                        // the source row
+#pragma unroll
+  for (int k = 0; k < CM_PPL; ++k) {
+    const int64_t xs = xs0 + k;
+    m[k] = (l[k] && xs >= 0 && xs < W) ? cell_id((int)pm[xs], Km) : 0;
+  }
+  u64* kt = keys + (size_t)(t - 1) * cap;
+  uint32_t* ct = cnt + (size_t)(t - 1) * cap;
+  int cl = 0, cm = 0;
+  uint32_t len = 0;
+  run = 0; flag = false;
+#pragma unroll
+  for (int k = 0; k < CM_PPL; ++k) {
+    if (m[k] != run) { run = m[k]; flag = run && os[run - 1]; }
+    const bool ok = l[k] && flag;
+    if (len && (!ok || l[k] != cl || m[k] != cm)) { cl_insert(kt, ct, cap - 1, cl, cm, len, status + t); len = 0; }
+    if (ok) { cl = l[k]; cm = m[k]; ++len; }
+  }
+  if (len) cl_insert(kt, ct, cap - 1, cl, cm, len, status + t);
+}
+
 // every table entry: best[cell] = max(count << 32 | ~m): the largest overlap, ties to the smallest m
 __global__ void cl_best_kernel(const u64* __restrict__ keys, const uint32_t* __restrict__ cnt, int64_t entries, uint32_t cap,
                                const int64_t* __restrict__ loff, u64* __restrict__ best) {
@@ -425,11 +492,12 @@ extern "C" size_t mseg_cell_links_workspace_bytes(int T, int64_t n_labels, int64
          mseg_align256((size_t)(n_labels + 1) * sizeof(u64));
 }
 
-// The three links calls.  shift == nullptr: same (y, x) in both frames (cl_pairs_kernel: both frames by vector loads);
-// tile == 0: shift is [T][2], one (dy, dx) per frame pair; else [T][ty][tx][2], one per tile x tile pixels of frame t
+// The four links calls.  shift == nullptr: same (y, x) in both frames (cl_pairs_kernel: both frames by vector loads);
+// tile == 0: shift is [T][2], one (dy, dx) per frame pair; else [T][ty][tx][2], one per tile x tile pixels of frame t.
+// want: frame t against frame t - gap, between the flagged cells only (cl_pairs_gap_kernel); nullptr: gap is 1, all cells
 static int cl_links(const void* labels, int dtype, int T, int H, int W, const int64_t* label_off, int64_t n_labels,
-                    int64_t table_cap, const int32_t* shift, int tile, int32_t* pred, int32_t* overlap, int32_t* status,
-                    void* ws, size_t ws_bytes, void* stream) {
+                    int64_t table_cap, const int32_t* shift, int tile, int gap, const uint8_t* want, const uint8_t* open,
+                    int32_t* pred, int32_t* overlap, int32_t* status, void* ws, size_t ws_bytes, void* stream) {
   if (!cell_stack_ok(labels, label_off, dtype, T, H, W, CM_PPL) || !status || !ws || n_labels < 0) return MSEG_EINVAL;
   if (n_labels > 0 && (!pred || !overlap)) return MSEG_EINVAL;
   const size_t need = mseg_cell_links_workspace_bytes(T, n_labels, table_cap);
@@ -445,15 +513,21 @@ static int cl_links(const void* labels, int dtype, int T, int H, int W, const in
   uint32_t* cnt = (uint32_t*)(b + mseg_align256(pairs * (size_t)cap * sizeof(u64)));
   u64* best = (u64*)((char*)cnt + mseg_align256(pairs * (size_t)cap * sizeof(uint32_t)));
   if (hipMemsetAsync(ws, 0, need, st) != hipSuccess) return MSEG_ELAUNCH;
-  if (T > 1) {
-    // lanes: 8 pixels each, in flat order without a shift, row by row with one
-    const int64_t lanes = shift ? (int64_t)(T - 1) * H * (((int64_t)W + CM_PPL - 1) / CM_PPL)
-                                : (int64_t)(T - 1) * (((int64_t)H * W + CM_PPL - 1) / CM_PPL);
+  if (T > gap) {
+    // lanes: 8 pixels each, in flat order without a shift, row by row with one and across a gap
+    const int64_t lanes = shift || want ? (int64_t)(T - gap) * H * (((int64_t)W + CM_PPL - 1) / CM_PPL)
+                                        : (int64_t)(T - 1) * (((int64_t)H * W + CM_PPL - 1) / CM_PPL);
     const dim3 grid(mseg_blocks(lanes, CM_BLOCK)), block(CM_BLOCK);
     cell_dispatch(dtype, [&](auto l) {
       typedef decltype(l) L;
       const L* lab = (const L*)labels;
-      if (!shift)
+      if (want && tile)
+        hipLaunchKernelGGL((cl_pairs_gap_kernel<L, true>), grid, block, 0, st, lab, T, H, W, label_off, gap, shift, tile, want,
+                           open, keys, cnt, cap, status);
+      else if (want)
+        hipLaunchKernelGGL((cl_pairs_gap_kernel<L, false>), grid, block, 0, st, lab, T, H, W, label_off, gap, shift, tile, want,
+                           open, keys, cnt, cap, status);
+      else if (!shift)
         hipLaunchKernelGGL(cl_pairs_kernel<L>, grid, block, 0, st, lab, T, H * W, label_off, keys, cnt, cap, status);
       else if (tile)
         hipLaunchKernelGGL((cl_pairs_shifted_kernel<L, true>), grid, block, 0, st, lab, T, H, W, label_off, shift, tile, keys,
@@ -475,22 +549,32 @@ static int cl_links(const void* labels, int dtype, int T, int H, int W, const in
 extern "C" int mseg_cell_links(const void* labels, int dtype, int T, int H, int W, const int64_t* label_off,
                                int64_t n_labels, int64_t table_cap, int32_t* pred, int32_t* overlap, int32_t* status,
                                void* ws, size_t ws_bytes, void* stream) {
-  return cl_links(labels, dtype, T, H, W, label_off, n_labels, table_cap, nullptr, 0, pred, overlap, status, ws, ws_bytes,
-                  stream);
+  return cl_links(labels, dtype, T, H, W, label_off, n_labels, table_cap, nullptr, 0, 1, nullptr, nullptr, pred, overlap,
+                  status, ws, ws_bytes, stream);
 }
 
 extern "C" int mseg_cell_links_shifted(const void* labels, int dtype, int T, int H, int W, const int64_t* label_off,
                                        int64_t n_labels, int64_t table_cap, const int32_t* shift, int32_t* pred,
                                        int32_t* overlap, int32_t* status, void* ws, size_t ws_bytes, void* stream) {
   if (!shift) return MSEG_EINVAL;
-  return cl_links(labels, dtype, T, H, W, label_off, n_labels, table_cap, shift, 0, pred, overlap, status, ws, ws_bytes,
-                  stream);
+  return cl_links(labels, dtype, T, H, W, label_off, n_labels, table_cap, shift, 0, 1, nullptr, nullptr, pred, overlap,
+                  status, ws, ws_bytes, stream);
 }
 
 extern "C" int mseg_cell_links_field(const void* labels, int dtype, int T, int H, int W, const int64_t* label_off,
                                      int64_t n_labels, int64_t table_cap, int tile, const int32_t* field, int32_t* pred,
                                      int32_t* overlap, int32_t* status, void* ws, size_t ws_bytes, void* stream) {
   if (!field || (tile != 64 && tile != 128 && tile != 256)) return MSEG_EINVAL;
-  return cl_links(labels, dtype, T, H, W, label_off, n_labels, table_cap, field, tile, pred, overlap, status, ws, ws_bytes,
-                  stream);
+  return cl_links(labels, dtype, T, H, W, label_off, n_labels, table_cap, field, tile, 1, nullptr, nullptr, pred, overlap,
+                  status, ws, ws_bytes, stream);
+}
+
+extern "C" int mseg_cell_links_gap(const void* labels, int dtype, int T, int H, int W, const int64_t* label_off,
+                                   int64_t n_labels, int64_t table_cap, int gap, int tile, const int32_t* shift,
+                                   const uint8_t* want, const uint8_t* open, int32_t* pred, int32_t* overlap,
+                                   int32_t* status, void* ws, size_t ws_bytes, void* stream) {
+  if (gap < 1 || gap > 5 || !want || !open) return MSEG_EINVAL;
+  if (shift ? (tile != 0 && tile != 64 && tile != 128 && tile != 256) : tile != 0) return MSEG_EINVAL;
+  return cl_links(labels, dtype, T, H, W, label_off, n_labels, table_cap, shift, tile, gap, want, open, pred, overlap, status,
+                  ws, ws_bytes, stream);
 }

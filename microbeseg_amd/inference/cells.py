@@ -5,15 +5,18 @@ per-cell values behind those means are what people who follow single microbes ne
 device (csrc/cells.hip: ``mseg_cell_measure``, ``mseg_cell_links``), every float of the table is derived
 from them here on the host in Python integers and fp64, so the table is exact where it can be and identical from run to
 run.  ``assemble_tracks`` turns the links into track ids: this is OVERLAP linking — a cell follows the cell of the
-previous frame it shares the most pixels with.  There is no motion model and no gap closing: a cell that moves further
-than its own extent between two frames, or that is missed in one frame, starts a new track.  ``drift=R`` takes the
+previous frame it shares the most pixels with.  There is no motion model, and no gap closing unless ``gap`` is given: a
+cell that moves further than its own extent between two frames, or that is missed in one frame, starts a new track.
+``gap=G`` joins a cell that was missed in up to G consecutive frames to its track again: after the ordinary links, the cells
+without predecessor look for a cell without successor 2 .. G + 1 frames back, under the motion summed over the gap
+(``close_gaps``, ``mseg_cell_links_gap``).  ``drift=R`` takes the
 usual cause of such jumps out first: the whole field of view moving by a few (tens of) pixels between time points.  The
 integer shift of every frame pair is the peak of the device's foreground-overlap surface (csrc/drift.hip:
 ``mseg_stack_drift``), and the links are taken under it (``mseg_cell_links_shifted``).  ``flow=r`` goes on
 from there for stacks whose cells move AGAINST EACH OTHER, as in a growing colony: every tile of every frame gets its own
 whole-pixel shift, the peak of the tile's overlap surface within +-r pixels of the pair's drift (``mseg_stack_flow``;
 DESIGN.md §6v), and the links are taken under that field (``mseg_cell_links_field``).  No sub-pixel or smoothed field, no
-rotation, no per-cell search, still no gap closing.  ``hull=True`` adds
+rotation, no per-cell search; gaps are closed by ``gap``, not by the field.  ``hull=True`` adds
 the measures of the cell's PIXEL OUTLINE people take from rod-shaped microbes: crack perimeter, convex hull, largest and
 smallest caliper (csrc/hull.hip: ``mseg_cell_hull``).  No sub-pixel contour is fitted.  ``midline=True`` adds the
 length along a BENT cell, where the largest caliper is only the chord: every cell is thinned alone to a one-pixel skeleton
@@ -60,6 +63,8 @@ MAX_PERCENTILES = 8   # 2 ranks each: the 16 ranks mseg_cell_order_stats accepts
 MAX_DRIFT = 128       # largest search radius mseg_stack_drift accepts
 MAX_FLOW = 32         # largest search radius mseg_stack_flow accepts
 FLOW_TILES = (64, 128, 256)    # the tile sizes mseg_stack_flow and mseg_cell_links_field accept
+GAP_COLUMNS = ['pred_gap']
+MAX_GAP = 4           # most consecutive missed frames ``gap`` closes: mseg_cell_links_gap looks up to MAX_GAP + 1 frames back
 NEIGHBOR_COLUMNS = ['contact_length', 'border_length', 'contact_fraction', 'n_touching', 'n_neighbors', 'nn_label',
                     'nn_distance', 'nn_gap', 'contact_label', 'contact_max']
 CONTACT_COLUMNS = ['frame', 'label_a', 'label_b', 'contact', 'distance']
@@ -74,9 +79,10 @@ SPOT_RECORD = np.dtype([('frame', '<i4'), ('channel', '<i4'), ('y', '<i4'), ('x'
 
 
 def columns(channels=(), link=True, drift=False, hull=False, midline=False, percentiles=(), neighbors=False, spots=False,
-            flow=False):
+            flow=False, gap=False):
     """the table's columns, in order, for the measured ``channels``; ``drift``: with the drift columns (needs ``link``);
-    ``flow``: with flow_y / flow_x after the drift columns (needs ``drift``);
+    ``flow``: with flow_y / flow_x after the drift columns (needs ``drift``); ``gap``: with pred_gap after the link, drift and
+    flow columns (needs ``link``);
     ``hull``: with the outline columns; ``midline``: with the midline columns; ``percentiles``: with p{P}_ch{c} for every
     measured channel (per channel the percentiles in the order given), then bg_p{P}_ch{c} likewise; ``neighbors``: with the
     neighbourhood columns; ``spots``: with the four spot columns of every measured channel, channel by channel; these come
@@ -85,11 +91,13 @@ def columns(channels=(), link=True, drift=False, hull=False, midline=False, perc
         raise ValueError("the drift columns belong to the link columns: drift needs link")
     if flow and not drift:
         raise ValueError("the flow columns follow the drift columns: flow needs drift")
+    if gap and not link:
+        raise ValueError("pred_gap belongs to the link columns: gap needs link")
     cols = list(SHAPE_COLUMNS)
     for c in channels:
         cols += [name.format(c=int(c)) for name in CHANNEL_COLUMNS]
     return cols + (list(LINK_COLUMNS) if link else []) + (list(DRIFT_COLUMNS) if drift else []) + \
-        (list(FLOW_COLUMNS) if flow else []) + \
+        (list(FLOW_COLUMNS) if flow else []) + (list(GAP_COLUMNS) if gap else []) + \
         (list(HULL_COLUMNS) if hull else []) + (list(MIDLINE_COLUMNS) if midline else []) + \
         [name.format(p=int(q), c=int(c)) for name in (PERCENTILE_COLUMNS if percentiles else ()) for c in channels
          for q in percentiles] + (list(NEIGHBOR_COLUMNS) if neighbors else []) + \
@@ -578,6 +586,142 @@ def link_raw(lab, pix, off, table_cap=None, shift=None, field=None, tile=None):
     return pred, ovl
 
 
+def check_gap(gap):
+    """the rule of ``measure_cells(gap=...)``, ``InferWorker.gap`` and --gap: None, or an int in 1 .. MAX_GAP"""
+    if gap is None:
+        return None
+    if isinstance(gap, bool) or not isinstance(gap, (int, np.integer)) or not 1 <= int(gap) <= MAX_GAP:
+        raise ValueError(f"gap: None or a whole number of missed frames in 1 .. {MAX_GAP} expected, got {gap!r}")
+    return int(gap)
+
+
+def compose_motion(moved, g):
+    """The motion over g frames: out[t] = moved[t] + moved[t - 1] + ... + moved[t - g + 1] for t >= g, zeros below.
+    ``moved``: the shifts of ``pick_drift`` [T, 2] or the field of ``pick_flow`` [T, ty, tx, 2] (entry 0 is never part of a
+    sum).  A field is summed per tile index: the tile of frame t keeps its index through the gap, which is an approximation
+    (the shifts are a few pixels, the tiles at least 64), not a composition through the displaced tile.  -> int32, pure numpy"""
+    moved = np.asarray(moved)
+    g = int(g)
+    if moved.ndim not in (2, 4) or moved.shape[-1] != 2 or g < 1:
+        raise ValueError(f"moved: [T, 2] or [T, ty, tx, 2] and g >= 1 expected, got {moved.shape} and {g}")
+    total = np.cumsum(moved.astype(np.int64), axis=0)
+    out = np.zeros(moved.shape, np.int32)
+    out[g:] = total[g:] - total[:max(len(total) - g, 0)]
+    return out
+
+
+def _links_gap_call(lab, pix, off, cap, g, want, open_, moved=None, tile=None, off_d=None):
+    lib = _lib.load()
+    dev = lab.device
+    T, H, W = (int(v) for v in lab.shape)
+    n = int(off[-1])
+    if off_d is None:
+        off_d = _offsets_to_device(off, dev)
+    # want, then open, in one upload; the byte after them keeps the tensor (and both addresses) valid for a stack without cells
+    flags = torch.from_numpy(np.concatenate([want, open_, [False]]).astype(np.uint8)).to(dev)
+    pred = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+    ovl = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+    status = torch.zeros(T, dtype=torch.int32, device=dev)
+    ws = _workspace(lib.mseg_cell_links_workspace_bytes(T, n, cap), dev,
+                    f"mseg_cell_links_gap: no workspace for T = {T}, {n} cells, table {cap}")
+    moved_d = torch.from_numpy(np.ascontiguousarray(moved, np.int32)).to(dev) if moved is not None else None
+    _lib.check(lib.mseg_cell_links_gap(lab.data_ptr(), pix, T, H, W, off_d.data_ptr(), n, cap, int(g),
+                                       int(tile) if tile is not None else 0,
+                                       moved_d.data_ptr() if moved_d is not None else None, flags.data_ptr(),
+                                       flags.data_ptr() + n, pred.data_ptr(), ovl.data_ptr(), status.data_ptr(),
+                                       ws.data_ptr(), ws.numel(), _stream(dev)), "cell_links_gap")
+    return pred.cpu().numpy()[:n], ovl.cpu().numpy()[:n], status.cpu().numpy()
+
+
+def link_gap_raw(lab, pix, off, g, want, open, shift=None, field=None, tile=None, table_cap=None, off_d=None):
+    """``mseg_cell_links_gap`` for the whole stack -> (pred int32 [n], overlap int32 [n]) on the host: per cell of frame t
+    flagged in ``want`` the cell of frame t - g flagged in ``open`` that shares the most pixels with it (ties to the smaller
+    label), 0 for every other cell.  ``want``, ``open``: bool [n] in ``off`` order.  ``shift`` int32 [T, 2], or ``field`` int32
+    [T, ty, tx, 2] with ``tile``: the motion of frame t against frame t - g, ALREADY composed (``compose_motion``); neither:
+    same (y, x).  The pair tables start at 4 entries per flagged cell of the two frames; a frame whose table filled up (the
+    device status word says so) is redone alone, on the g + 1 frames t - g .. t, with a table of more than H * W entries,
+    which cannot fill up: the result is always exact.  ``off_d``: ``off`` on the device already (``close_gaps`` uploads it once
+    for all its passes), or None."""
+    T, H, W = (int(v) for v in lab.shape)
+    g = int(g)
+    off = np.asarray(off, np.int64)
+    n = int(off[-1])
+    if (field is None) != (tile is None) or (field is not None and shift is not None):
+        raise ValueError("field and tile go together, and not with shift")
+    if not 1 <= g <= MAX_GAP + 1:
+        raise ValueError(f"g: 1 .. {MAX_GAP + 1} frames back expected, got {g}")
+    want, open_ = np.asarray(want, bool), np.asarray(open, bool)
+    if want.shape != (n,) or open_.shape != (n,):
+        raise ValueError(f"want and open: bool [{n}] expected, got {want.shape} and {open_.shape}")
+    moved = None
+    if field is not None:
+        moved = np.ascontiguousarray(field, np.int32)
+        if int(tile) not in FLOW_TILES or moved.shape != (T, -(-H // int(tile)), -(-W // int(tile)), 2):
+            raise ValueError(f"field: int32 [{T}, ceil({H} / tile), ceil({W} / tile), 2] with a tile of {FLOW_TILES} expected, "
+                             f"got {moved.shape} with tile {tile}")
+    elif shift is not None:
+        moved = np.ascontiguousarray(shift, np.int32)
+        if moved.shape != (T, 2):
+            raise ValueError(f"shift: int32 [{T}, 2] expected, got {moved.shape}")
+    if table_cap is None:
+        frame = np.repeat(np.arange(T), np.diff(off))
+        nw, no = np.bincount(frame[want], minlength=T), np.bincount(frame[open_], minlength=T)
+        pair = int((nw[g:] + no[:T - g]).max()) if T > g else 0
+        table_cap = min(max(MIN_TABLE, _pow2(4 * pair)), _pow2(H * W + 1))
+    pred, ovl, status = _links_gap_call(lab, pix, off, int(table_cap), g, want, open_, moved, tile, off_d)
+    pred, ovl = pred.copy(), ovl.copy()
+    for t in np.nonzero(status)[0]:
+        lo, hi = int(off[t - g]), int(off[t + 1])
+        sub = off[t - g:t + 2] - lo
+        p2, o2, s2 = _links_gap_call(lab[t - g:t + 1], pix, sub, max(MIN_TABLE, _pow2(H * W + 1)), g, want[lo:hi],
+                                     open_[lo:hi], None if moved is None else moved[t - g:t + 1], tile)
+        if s2.any():
+            raise RuntimeError("mseg_cell_links_gap: a table of more than H * W entries reported full")
+        pred[off[t]:off[t + 1]] = p2[sub[g]:]
+        ovl[off[t]:off[t + 1]] = o2[sub[g]:]
+    return pred, ovl
+
+
+def close_gaps(lab, pix, off, pred, overlap, min_overlap, G, shift=None, field=None, tile=None):
+    """ Gap closing after the ordinary links -> (pred int32 [n], overlap int32 [n], pred_gap int32 [n]).
+
+    ``pred``, ``overlap``: the links of ``link_raw``; a link counts as accepted when ``overlap >= min_overlap``.  An ORPHAN
+    is a cell without accepted predecessor, an OPEN END a cell that no cell names as its accepted predecessor.  One pass per
+    g = 2 .. G + 1, in that order: the orphans of the frames t >= g look among the open ends of frame t - g, pixel (y, x)
+    against (y - Dy, x - Dx) with D the motion summed over the g frames (``compose_motion`` of ``shift``, or of ``field``
+    with ``tile``; neither: 0); per orphan the open end sharing the most pixels wins, ties to the smaller label
+    (``link_gap_raw``: one ``mseg_cell_links_gap`` call per pass); the link stands when its overlap is >= ``min_overlap``.
+    Cells that continued take no part, on either side.  After a pass the linked orphans and their predecessors leave the
+    sets; two orphans of one frame that found the same open end both keep it: a division across the gap.  The sets are
+    O(cells) host work between the passes.  pred_gap: 0 where pred is 0, 1 for an ordinary link (one that ``min_overlap``
+    rejects included, as pred / overlap keep it), g for a closed gap: pred then names a label of frame t - g.  A slot
+    without pixels overlaps nothing, so it is flagged without effect."""
+    off = np.asarray(off, np.int64)
+    T, n = len(off) - 1, int(off[-1])
+    pred, overlap = np.array(pred, np.int32), np.array(overlap, np.int32)
+    frame = np.repeat(np.arange(T, dtype=np.int64), np.diff(off))
+    pred_gap = (pred > 0).astype(np.int32)
+    linked = (pred > 0) & (overlap >= int(min_overlap))
+    orphan, open_ = ~linked, np.ones(n, bool)
+    open_[off[frame[linked] - 1] + pred[linked] - 1] = False
+    moved = field if field is not None else shift
+    off_d = None                      # the offsets go up once, with the first pass that has something to look for
+    for g in range(2, int(G) + 2):
+        want = orphan & (frame >= g)
+        if g >= T or not want.any() or not open_[:off[T - g]].any():
+            continue
+        over = compose_motion(moved, g) if moved is not None else None
+        if off_d is None:
+            off_d = _offsets_to_device(off, lab.device)
+        p, o = link_gap_raw(lab, pix, off, g, want, open_, shift=over if field is None else None,
+                            field=over if field is not None else None, tile=tile, off_d=off_d)
+        hit = want & (p > 0) & (o >= int(min_overlap))
+        pred[hit], overlap[hit], pred_gap[hit] = p[hit], o[hit], g
+        orphan[hit] = False
+        open_[off[frame[hit] - g] + p[hit] - 1] = False
+    return pred, overlap, pred_gap
+
+
 def check_neighbors(r):
     """the rule of ``measure_cells(neighbors=...)``, ``InferWorker.neighbors`` and --neighbors: None, or an int in 1 ..
     MAX_NEIGHBOR_RADIUS"""
@@ -864,7 +1008,7 @@ def _spot_sums(records, off, n_channels):
     return {(k // n, k % n): (m, (h << 32) + l) for k, m, l, h in zip(keys.tolist(), top.tolist(), lo.tolist(), hi.tolist())}
 
 
-def assemble_tracks(frame, label, pred, overlap, min_overlap=1):
+def assemble_tracks(frame, label, pred, overlap, min_overlap=1, gap=None):
     """ Track ids from overlap links; pure host code, O(cells).
 
     ``frame``, ``label``, ``pred``, ``overlap``: one entry per cell, in (frame, label) order; ``pred`` names a label of the
@@ -872,18 +1016,21 @@ def assemble_tracks(frame, label, pred, overlap, min_overlap=1):
     name m: a cell whose predecessor has exactly one successor inherits its track_id and parent_track; a cell whose
     predecessor has two or more successors starts a new track whose parent_track is the predecessor's track (a division);
     a cell without predecessor starts a new track with parent_track 0.  Track ids count from 1 in order of first
-    appearance.  A cell that loses a merge has no successor: its track ends.
+    appearance.  A cell that loses a merge has no successor: its track ends.  ``gap``: per cell the number of frames back
+    to its predecessor (``close_gaps``' pred_gap; entries of cells without one are not read), None: 1 everywhere.  The
+    rules do not look at it: a predecessor with exactly one successor hands on its track whatever the gap.
 
-    Overlap linking only: no motion model, no gap closing.
+    Overlap linking only: no motion model; gaps are closed before, by ``close_gaps``, not here.
     :return: (track_id int64 [n], parent_track int64 [n])
     """
     frame, label = np.asarray(frame, np.int64), np.asarray(label, np.int64)
     pred = np.where(np.asarray(overlap, np.int64) >= int(min_overlap), np.asarray(pred, np.int64), 0)
+    back = np.ones(len(frame), np.int64) if gap is None else np.asarray(gap, np.int64)
     index = {(int(f), int(l)): i for i, (f, l) in enumerate(zip(frame, label))}
     src = np.full(len(frame), -1, np.int64)
-    for i, (f, p) in enumerate(zip(frame, pred)):
+    for i, (f, p, b) in enumerate(zip(frame, pred, back)):
         if p > 0:
-            src[i] = index.get((int(f) - 1, int(p)), -1)
+            src[i] = index.get((int(f) - int(b), int(p)), -1)
     n_succ = np.bincount(src[src >= 0], minlength=len(frame))
     track, parent = np.zeros(len(frame), np.int64), np.zeros(len(frame), np.int64)
     nxt = 1
@@ -943,7 +1090,7 @@ def _neighborhood(v):
 
 
 def table_from_sums(off, H, W, raw, channels=(), links=None, min_overlap=1, shift=None, hull=None, midline=None,
-                    order_stats=None, neighbors=None, spots=None, field=None, tile=None):
+                    order_stats=None, neighbors=None, spots=None, field=None, tile=None, gaps=None):
     """the DataFrame from the integer sums of ``measure_raw`` (and ``links`` = (pred, overlap) or None); host arithmetic in
     Python integers and fp64.  ``shift``: int [T, 2], the (dy, dx) of every frame against its predecessor the links were
     taken under (row 0 ignored), or None: with it the drift columns follow the link columns.  ``hull``: int [10, n], the
@@ -967,7 +1114,9 @@ def table_from_sums(off, H, W, raw, channels=(), links=None, min_overlap=1, shif
     without a spot), spot_sum_ch{c} = the exact integer sum of their D / 16^(2 scale) (0 without), bg_spots_ch{c} = bg_count
     of the frame.  ``field`` with ``tile``: int [T, ty, tx, 2], the field of ``pick_flow`` the links were taken under (needs
     ``shift``), or None: with it flow_y / flow_x follow the drift columns: the field value of the tile that holds the pixel
-    (floor(centroid_y), floor(centroid_x)), 0 in frame 0"""
+    (floor(centroid_y), floor(centroid_x)), 0 in frame 0.  ``gaps``: int [n], the pred_gap of ``close_gaps`` (with its pred and
+    overlap as ``links``), or None: with it pred_gap follows the link, drift and flow columns and the tracks are assembled
+    over the gaps"""
     off = np.asarray(off, np.int64)
     area = raw["shape"][0]
     if field is not None and shift is None:
@@ -978,7 +1127,7 @@ def table_from_sums(off, H, W, raw, channels=(), links=None, min_overlap=1, shif
     if spots is not None and not len(channels):
         raise ValueError("spots are taken of an image's channels: none is measured")
     rows = {c: [] for c in columns(channels, links is not None, shift is not None, hull is not None, midline is not None, pct,
-                                   neighbors is not None, spots is not None, field is not None)}
+                                   neighbors is not None, spots is not None, field is not None, gaps is not None)}
     if field is not None:
         field = np.asarray(field, np.int64).copy()
         field[0] = 0
@@ -1030,6 +1179,8 @@ def table_from_sums(off, H, W, raw, channels=(), links=None, min_overlap=1, shif
                 vals += [total[t][0], total[t][1], sh[1][s] / n - total[t][0], sh[2][s] / n - total[t][1]]
             if field is not None:
                 vals += field[t][sh[1][s] // n // tile][sh[2][s] // n // tile]
+            if gaps is not None:
+                vals += [int(gaps[s])]
             if hull is not None:
                 vals += _outline(n, [plane[s] for plane in hl])
             if midline is not None:
@@ -1049,12 +1200,13 @@ def table_from_sums(off, H, W, raw, channels=(), links=None, min_overlap=1, shif
     assert int((area > 0).sum()) == len(df)
     if links is not None:
         df["track_id"], df["parent_track"] = assemble_tracks(df["frame"], df["label"], df["pred_label"], df["overlap"],
-                                                             min_overlap)
+                                                             min_overlap, df["pred_gap"] if gaps is not None else None)
     return df
 
 
 def measure_cells(mask, img=None, channels=None, link=True, min_overlap=1, device=None, drift=None, hull=False,
-                  midline=False, percentiles=None, neighbors=None, spots=None, spot_scale=2, flow=None, flow_tile=64):
+                  midline=False, percentiles=None, neighbors=None, spots=None, spot_scale=2, flow=None, flow_tile=64,
+                  gap=None):
     """ One row per cell of a segmented stack, ordered by (frame, label).
 
     :param mask: label stack [T, H, W] (or one frame [H, W]): host array or device tensor (int16 holding uint16 bits, or
@@ -1063,7 +1215,8 @@ def measure_cells(mask, img=None, channels=None, link=True, min_overlap=1, devic
         device tensor; read in place), or None for the shape and link columns only.
     :param channels: indices into the channel axis of ``img`` to measure (default: all); they name the columns.
     :param link: add pred_label / overlap (the label of the previous frame sharing the most pixels, ties to the smaller
-        label, 0 = none) and track_id / parent_track (``assemble_tracks``).  Overlap linking: no motion model, no gap closing.
+        label, 0 = none) and track_id / parent_track (``assemble_tracks``).  Overlap linking: no motion model, and no gap
+        closing unless ``gap`` is given.
     :param min_overlap: links with fewer shared pixels are dropped before the tracks are assembled.
     :param drift: None (default): link at the same (y, x).  R, a whole number in 0 .. 128: take the stage drift out first.
         Every frame pair gets the integer shift (|dy|, |dx| <= R) under which the foregrounds of the two frames share the
@@ -1077,9 +1230,19 @@ def measure_cells(mask, img=None, channels=None, link=True, min_overlap=1, devic
         that field, and flow_y / flow_x follow the drift columns: the field value of the tile that holds the cell's
         centroid pixel, i.e. the cell's estimated motion against the previous frame, stage drift included (0 in frame 0).
         drift_y / drift_x and the registered centroids stay the global ones.  Whole pixels, one shift per tile: no
-        smoothing or interpolation of the field, no rotation, no per-cell search, no gap closing.  Needs ``drift``.
+        smoothing or interpolation of the field, no rotation, no per-cell search; gaps are ``gap``'s.  Needs ``drift``.
     :param flow_tile: 64 (default), 128 or 256: the tile edge in pixels.  Small tiles follow a steep field, large tiles
         hold more cells to vote.  Read only with ``flow``.
+    :param gap: None (default): a cell that is missed in one frame starts a new track.  G, a whole number in 1 .. 4: close
+        gaps of up to G consecutive missed frames (``close_gaps``).  After the ordinary links, every cell without an
+        accepted predecessor looks 2, then 3, .. G + 1 frames back among the cells that nothing followed, at the same
+        (y, x) or, with ``drift`` / ``flow``, under the shifts summed over the gap (for a field per tile index: an
+        approximation); the cell sharing the most pixels wins when it shares at least ``min_overlap``.  pred_label then
+        names a label of frame ``frame - pred_gap``, overlap is the overlap under the summed motion, and the new column
+        pred_gap (0 without predecessor, 1 for an ordinary link, g for a closed gap) follows the link, drift and flow
+        columns.  The track goes on across the gap; two cells that find the same ended cell are a division.  No motion
+        model, no per-cell search, no rows for the missed frames, no check that the skipped frames are empty under the
+        cell.  Needs ``link``.
     :param hull: True: the table ends with the measures of every cell's pixel outline (HULL_COLUMNS): the crack perimeter,
         the area of the convex hull of the pixel corners and the solidity, the largest caliper (Feret diameter) with its
         angle and end points, and the smallest caliper.  The cell is the union of its pixel squares: no sub-pixel contour
@@ -1117,7 +1280,7 @@ def measure_cells(mask, img=None, channels=None, link=True, min_overlap=1, devic
     :param spot_scale: s, a whole number in 1 .. 5 (default 2): the band-pass is the difference of two binomial smoothings
         with sigma = sqrt(s / 2) and sqrt(s) pixels: foci of about that radius answer best.  Read only with ``spots``.
     :return: pandas.DataFrame with the columns of ``columns(channels, link, drift is not None, hull, midline, percentiles,
-        neighbors is not None, spots is not None, flow is not None)``.
+        neighbors is not None, spots is not None, flow is not None, gap is not None)``.
     """
     drift = check_drift(drift)
     flow, flow_tile = check_flow(flow, flow_tile)
@@ -1132,6 +1295,9 @@ def measure_cells(mask, img=None, channels=None, link=True, min_overlap=1, devic
         raise ValueError("spots are taken of an image's channels: no image given")
     if drift is not None and not link:
         raise ValueError("drift changes how cells are linked: it needs link=True")
+    gap = check_gap(gap)
+    if gap is not None and not link:
+        raise ValueError("gap closes gaps in the links: it needs link=True")
     dev = _device(device)
     with torch.cuda.device(dev):
         lab, pix = _labels_to_device(mask, dev)
@@ -1159,6 +1325,10 @@ def measure_cells(mask, img=None, channels=None, link=True, min_overlap=1, devic
             links = link_raw(lab, pix, off, field=field, tile=flow_tile)
         else:
             links = link_raw(lab, pix, off, shift=shift) if link else None
+        gaps = None
+        if gap is not None:
+            *links, gaps = close_gaps(lab, pix, off, *links, min_overlap, gap, shift if field is None else None, field,
+                                      flow_tile if field is not None else None)
         outline = hull_raw(lab, pix, off, raw["bbox"]) if hull else None
         skel = midline_raw(lab, pix, off, raw["bbox"]) if midline else None
         stats = None
@@ -1169,7 +1339,7 @@ def measure_cells(mask, img=None, channels=None, link=True, min_overlap=1, devic
         near = neighbors_raw(lab, pix, off, neighbors)[0] if neighbors is not None else None
         foci = (spots[1],) + spots_raw(lab, pix, off, image, channels, *spots) if spots is not None else None
     return table_from_sums(off, H, W, raw, channels, links, min_overlap, shift, outline, skel, stats, near, foci, field,
-                           flow_tile if field is not None else None)
+                           flow_tile if field is not None else None, gaps)
 
 
 def write_cells(df, csv_path):

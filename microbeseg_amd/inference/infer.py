@@ -101,6 +101,10 @@ class InferWorker(QObject):
     # cells are linked under that field (inference/cells.py)
     flow = None
     flow_tile = 64
+    # [extension] cell_table: None = a cell that is missed in a frame starts a new track; G = 1 .. 4: a cell missed in up to G
+    # consecutive frames is linked to the cell that ended there, 2 .. G + 1 frames back, under the drift / flow summed over
+    # the gap, and the table gains pred_gap (inference/cells.py)
+    gap = None
     # [extension] cell_table: True = the table ends with the outline measures of every cell (perimeter, convex hull, Feret
     # length / width / angle; inference/cells.py)
     hull = False
@@ -897,7 +901,8 @@ class InferWorker(QObject):
         """ [extension] The per-cell table of a segmented stack (inference/cells.py ``measure_cells``): ``results`` are the
         masks of ``infer_stack``, ``img`` the [T, C, H, W] image (a strided view is read in place) whose ``channels``
         (numbers of the source image, they name the columns) are measured.  Overlap linking: no motion model, no gap
-        closing; with ``self.drift`` set, under the estimated stage drift of every frame pair; with ``self.flow`` set as well, under a
+        closing unless ``self.gap`` is set (then across up to that many missed frames); with ``self.drift`` set, under the
+        estimated stage drift of every frame pair; with ``self.flow`` set as well, under a
         tile-wise displacement field around it (tiles of ``self.flow_tile`` pixels); with ``self.hull`` set, with
         the outline columns; with ``self.midline`` set, with the midline columns; with ``self.percentiles`` set, with the
         percentile columns; with ``self.neighbors`` set, with the neighbourhood columns; with ``self.spots`` set, with the
@@ -905,7 +910,8 @@ class InferWorker(QObject):
         from .cells import measure_cells
         df = measure_cells(results, img, link=True, min_overlap=self.min_overlap, device=self.device, drift=self.drift,
                            hull=self.hull, midline=self.midline, percentiles=self.percentiles, neighbors=self.neighbors,
-                           spots=self.spots, spot_scale=self.spot_scale, flow=self.flow, flow_tile=self.flow_tile)
+                           spots=self.spots, spot_scale=self.spot_scale, flow=self.flow, flow_tile=self.flow_tile,
+                           gap=self.gap)
         if img is not None and channels is not None:      # the view holds the chosen channels only: name them by source
             names = {f'{k}_ch{i}': f'{k}_ch{int(c)}' for i, c in reversed(list(enumerate(channels)))
                      for k in ('mean', 'std', 'min', 'max', 'sum', 'bg_mean') +
