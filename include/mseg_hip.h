@@ -519,7 +519,8 @@ int mseg_eval_pair_counts(const int32_t* true_lab, const int32_t* pred_lab, int 
  * mseg_region_stats: per frame t and label l in 1..K_t (K_t = label_off[t+1] - label_off[t], label_off on the device,
  *   label_off[T] = n_labels) the regionprops area / axis_major_length / axis_minor_length (analysis.py:158-164) at index
  *   label_off[t] + l - 1 (area 0: label absent), and total_area[t] = the sum of all label values of frame t (np.sum of the
- *   mask, analysis.py:156).  Integer moment sums with 64-bit atomics (deterministic).
+ *   mask, analysis.py:156).  Integer moment sums with 64-bit atomics (deterministic).  Every sum is exact whenever its
+ *   true value fits uint64, at any frame width.
  * mseg_overlay_rgb: out = uint8(clip(255 * f32(img) / max(img), 0, 255)) with outline pixels (255, 255, 0)
  *   (result_export.py:183-190); img uint8 / uint16 [T][H][W] (C == 1; out [T][H][W][3]) or [T][H][W][C] with C >= 3
  *   (out [T][H][W][C], channels 0..2 of outline pixels replaced).  The maximum is taken over the stack on the device.    */
@@ -553,6 +554,7 @@ int mseg_overlay_rgb(const void* img, int dtype, int T, int H, int W, int C, con
  *     bg_sums    uint64 [3][T][C]         count, sum and sum of squares over the background (label 0) of a frame
  *     bg_minmax  uint32 [2][T][C]         its min and max
  *   An absent cell has zeros everywhere (bbox and min included), and so has a frame without background pixels.
+ *   Every sum is exact whenever its true value fits uint64, at any frame width.
  * mseg_cell_links: for every frame t >= 1 and cell l of it, pred[slot] = the label m of frame t - 1 (1 <= m <= K_{t-1})
  *   that shares the most pixels (same y, x) with l, ties to the smallest m, 0 where nothing overlaps; overlap[slot] = that
  *   pixel count; frame 0 gets zeros.  The (l, m) pairs of a frame pair are counted in an open-addressing table of

@@ -211,14 +211,12 @@ __global__ void rs_runs_kernel(const int32_t* __restrict__ lab, int T, int H, in
   const unsigned long long len = (unsigned long long)(e - x + 1);
   const unsigned long long yy = (unsigned long long)y, a = (unsigned long long)x, b = (unsigned long long)e;
   const unsigned long long sx = (a + b) * len / 2;
-  // sum_{v=a}^{b} v^2 = S(b) - S(a - 1), S(m) = m (m + 1) (2m + 1) / 6
-  const unsigned long long sb = b * (b + 1) * (2 * b + 1) / 6, sa = a == 0 ? 0ull : (a - 1) * a * (2 * a - 1) / 6;
   const size_t s = (size_t)(loff[t] + l - 1);
   atomicAdd(&area[s], len);
   atomicAdd(&mom[s].sy, yy * len);
   atomicAdd(&mom[s].sx, sx);
   atomicAdd(&mom[s].syy, yy * yy * len);
-  atomicAdd(&mom[s].sxx, sb - sa);
+  atomicAdd(&mom[s].sxx, run_sum_sq(a, b));
   atomicAdd(&mom[s].sxy, yy * sx);
   atomicAdd(&total_area[t], (unsigned long long)l * len);
 }

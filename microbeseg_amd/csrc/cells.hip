@@ -67,13 +67,12 @@ __device__ __forceinline__ void cm_flush_run(const CmOut& o, int64_t s, int y, i
   if (shape) {
     const u64 yy = (u64)y, a = (u64)x0, b = a + len - 1;
     const u64 sx = (a + b) * len / 2;
-    const u64 sb = b * (b + 1) * (2 * b + 1) / 6, sa = a == 0 ? 0ull : (a - 1) * a * (2 * a - 1) / 6;
     const int64_t n = o.n;
     atomicAdd(&o.shape[s], len);
     atomicAdd(&o.shape[n + s], yy * len);
     atomicAdd(&o.shape[2 * n + s], sx);
     atomicAdd(&o.shape[3 * n + s], yy * yy * len);
-    atomicAdd(&o.shape[4 * n + s], sb - sa);
+    atomicAdd(&o.shape[4 * n + s], run_sum_sq(a, b));
     atomicAdd(&o.shape[5 * n + s], yy * sx);
     int32_t* bb = o.bbox + 4 * s;
     atomicMin(&bb[0], y);

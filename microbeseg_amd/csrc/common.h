@@ -225,6 +225,25 @@ __device__ __forceinline__ float clamp_lo(float v, float lo) {
   return r;
 }
 
+// sum of v^2 over the columns v = a .. b of a horizontal run (a <= b < 2^31): S(b) - S(a - 1), S(m) = m (m + 1) (2m + 1) / 6.
+// The product m (m + 1) (2m + 1) passes 64 bits from m = 2^21 on, and dividing a wrapped product by 6 gives nonsense: a run
+// that reaches such a column (a rare, divergent branch) takes S from sum_sq_wide instead.  Frames of up to 2^21 columns take
+// the old 64-bit line only.
+// S(m) modulo 2^64 for m < 2^31: the divisions come first and are exact (the even one of m, m + 1 is halved; 3 divides m,
+// m + 1 or 2m + 1 as m = 0, 2, 1 mod 3), all three factors still fit 32 bits, and only then the product is taken, which may
+// wrap.  The difference of two such values is the true sum modulo 2^64: the true sum whenever that fits uint64.
+__device__ __forceinline__ unsigned long long sum_sq_wide(unsigned m) {
+  unsigned p = m, q = m + 1, r = 2 * m + 1;
+  if (p & 1) q >>= 1; else p >>= 1;
+  const unsigned rem = m % 3;
+  if (rem == 0) p /= 3; else if (rem == 2) q /= 3; else r /= 3;
+  return (unsigned long long)p * q * r;
+}
+__device__ __forceinline__ unsigned long long run_sum_sq(unsigned long long a, unsigned long long b) {
+  if (b < (1ull << 21)) return b * (b + 1) * (2 * b + 1) / 6 - (a == 0 ? 0ull : (a - 1) * a * (2 * a - 1) / 6);
+  return sum_sq_wide((unsigned)b) - (a == 0 ? 0ull : sum_sq_wide((unsigned)a - 1));
+}
+
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

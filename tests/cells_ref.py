@@ -67,6 +67,79 @@ def links(labels, off):
     return pred, overlap
 
 
+# ---- the same two contracts without a loop over the labels: for stacks of millions of pixels and tens of thousands of ids ----
+# Integers only: every sum is taken in uint64 (np.add.reduceat over the pixels sorted by slot), which is exact as long as the
+# true value fits 64 bits.  tests/test_cells_structured_host.py holds them against measure / links above.
+def _slots(labels, off):
+    """-> (t, p, slot) of the pixels that are a cell of their frame, sorted by slot (stable: by t, p within a slot)"""
+    T, H, W = labels.shape
+    lab = labels.reshape(T, H * W).astype(np.int64)
+    K = np.diff(np.asarray(off, np.int64))
+    t, p = np.nonzero((lab > 0) & (lab <= K[:, None]))
+    slot = np.asarray(off, np.int64)[t] + lab[t, p] - 1
+    order = np.argsort(slot, kind="stable")
+    return t[order], p[order], slot[order]
+
+
+def measure_fast(labels, off, img=None):
+    """measure(labels, off, img): same contract, same names, layouts and dtypes"""
+    T, H, W = labels.shape
+    n = int(off[-1])
+    C = 0 if img is None else img.shape[1]
+    out = {"shape": np.zeros((6, n), np.uint64), "bbox": np.zeros((n, 4), np.int32),
+           "ch_sums": np.zeros((2, C, n), np.uint64), "ch_minmax": np.zeros((2, C, n), np.uint32),
+           "bg_sums": np.zeros((3, T, C), np.uint64), "bg_minmax": np.zeros((2, T, C), np.uint32)}
+    t, p, slot = _slots(labels, off)
+    if slot.size:
+        first = np.flatnonzero(np.r_[True, slot[1:] != slot[:-1]])
+        s = slot[first]
+        y, x = (p // W).astype(np.uint64), (p % W).astype(np.uint64)
+        for j, v in enumerate((np.ones_like(y), y, x, y * y, x * x, x * y)):
+            out["shape"][j, s] = np.add.reduceat(v, first)
+        out["bbox"][s, 0], out["bbox"][s, 1] = np.minimum.reduceat(y, first), np.minimum.reduceat(x, first)
+        out["bbox"][s, 2], out["bbox"][s, 3] = np.maximum.reduceat(y, first) + 1, np.maximum.reduceat(x, first) + 1
+        for c in range(C):
+            v = img[:, c].reshape(T, H * W)[t, p].astype(np.uint64)
+            out["ch_sums"][0, c, s], out["ch_sums"][1, c, s] = np.add.reduceat(v, first), np.add.reduceat(v * v, first)
+            out["ch_minmax"][0, c, s], out["ch_minmax"][1, c, s] = np.minimum.reduceat(v, first), np.maximum.reduceat(v, first)
+    if C:
+        bg = labels.reshape(T, H * W) == 0
+        has = bg.any(axis=1)
+        for c in range(C):
+            v = img[:, c].reshape(T, H * W).astype(np.uint64)
+            out["bg_sums"][0, :, c] = bg.sum(axis=1, dtype=np.uint64)
+            out["bg_sums"][1, :, c] = (v * bg).sum(axis=1, dtype=np.uint64)
+            out["bg_sums"][2, :, c] = (v * v * bg).sum(axis=1, dtype=np.uint64)
+            out["bg_minmax"][0, :, c] = np.where(has, np.where(bg, v, np.uint64(2 ** 32)).min(axis=1), 0)
+            out["bg_minmax"][1, :, c] = np.where(bg, v, np.uint64(0)).max(axis=1)
+    return out
+
+
+def pairs(labels, off, t):
+    """the distinct (l, m) pairs of frame t over frame t - 1, both cells of their frames -> (l, m, count), sorted by l, m"""
+    T, H, W = labels.shape
+    l, m = labels[t].ravel().astype(np.int64), labels[t - 1].ravel().astype(np.int64)
+    ok = (l > 0) & (l <= int(off[t + 1] - off[t])) & (m > 0) & (m <= int(off[t] - off[t - 1]))
+    key, count = np.unique(l[ok] << 32 | m[ok], return_counts=True)
+    return key >> 32, key & 0xFFFFFFFF, count
+
+
+def links_fast(labels, off):
+    """links(labels, off): same contract and layouts"""
+    n = int(off[-1])
+    pred, overlap = np.zeros(n, np.int32), np.zeros(n, np.int32)
+    for t in range(1, labels.shape[0]):
+        l, m, count = pairs(labels, off, t)
+        if l.size == 0:
+            continue
+        order = np.lexsort((m, -count, l))                     # per l: the largest count first, the smallest m of a tie first
+        l, m, count = l[order], m[order], count[order]
+        first = np.flatnonzero(np.r_[True, l[1:] != l[:-1]])
+        s = int(off[t]) + l[first] - 1
+        pred[s], overlap[s] = m[first], count[first]
+    return pred, overlap
+
+
 def tracks(frame, label, pred, overlap, min_overlap):
     """the track rules of the issue, restated with dictionaries"""
     cells = list(zip((int(f) for f in frame), (int(l) for l in label)))
