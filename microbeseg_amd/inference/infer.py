@@ -7,6 +7,7 @@ kept is the per-frame contract — ``inference(img, min_val, max_val, pads)`` wi
 ``np.uint16`` instance mask of the un-padded frame — plus ``infer_stack`` for local [T, H, W] stacks.
 On the MI355X path the frame stays in HBM between the network and the watershed; only the uint16 mask returns.
 """
+import itertools
 import json
 from pathlib import Path
 
@@ -46,6 +47,21 @@ def frame_batch_for(Hp, Wp, requested):
     if req <= 0:
         req = FRAME_BATCH_AUTO
     return max(1, min(req, cap))
+
+
+def normalize_host(frame, min_val, max_val):
+    """2 * (f32(frame) - min) / (max - min) - 1 on the host, same operation order and scalar types as infer.py:346-348
+    (``min_val`` / ``max_val``: numpy scalars of the frame's dtype); the device normalisation equals it bit for bit"""
+    return 2 * (frame.astype(np.float32) - min_val) / (max_val - min_val) - 1
+
+
+def hook_per_frame(hook, pred):
+    """``hook`` once per frame, in frame order, on that frame's (1, C, Hp, Wp) slice of a group's padded prediction
+    (boundary models: logits (n, 3, Hp, Wp); distance models: (border, cell), each (n, 1, Hp, Wp)), concatenated again"""
+    if isinstance(pred, torch.Tensor):
+        return torch.cat([hook(pred[i:i + 1]) for i in range(pred.shape[0])], dim=0)
+    hooked = [hook((pred[0][i:i + 1], pred[1][i:i + 1])) for i in range(pred[0].shape[0])]
+    return torch.cat([h[0] for h in hooked], dim=0), torch.cat([h[1] for h in hooked], dim=0)
 
 
 def load_model(model, device):
@@ -187,8 +203,7 @@ class InferWorker(QObject):
         if self.tta != 1:               # the padding is the frame's own: every member is padded in its orientation
             return self._infer_stack_tta(np.asarray(img)[None, pads[0]:, pads[1]:])[0]
         self.net.eval()
-        # 2 * (f32(img) - min) / (max - min) - 1, same operation order and scalar types as infer.py:346-348
-        img_batch = 2 * (img.astype(np.float32) - min_val) / (max_val - min_val) - 1
+        img_batch = normalize_host(img, min_val, max_val)
         img_batch = torch.from_numpy(np.ascontiguousarray(img_batch[None, None, :, :])).to(torch.float)
         with torch.no_grad():   # the reference disables autograd globally (infer.py:343); here only for the call
             pred = self._forward(img_batch)
@@ -214,7 +229,6 @@ class InferWorker(QObject):
 
     def _postprocess(self, pred, pads):
         """prediction (device) -> uint16 labels of the un-padded frame (device tensor, int16 storage)"""
-        lib = _lib.load()
         if self.model_settings['label_type'] == 'distance':
             border, cell = pred
             cell = cell[0, 0, pads[0]:, pads[1]:].contiguous()
@@ -237,11 +251,73 @@ class InferWorker(QObject):
                                          torch.cuda.current_stream().cuda_stream), "softmax3_hwc")
         return probs
 
+    @staticmethod
+    def _softmax_group(logits, pads):
+        """contiguous (m, 3, Hp, Wp) logits -> (m, H, W, 3) softmax probabilities of the un-padded frames (current stream)"""
+        lib = _lib.load()
+        m, _, hp, wp = logits.shape
+        probs = torch.empty((m, hp - pads[0], wp - pads[1], 3), dtype=torch.float32, device=logits.device)
+        stream = torch.cuda.current_stream().cuda_stream
+        for j in range(m):
+            _lib.check(lib.mseg_softmax3_hwc(logits[j].data_ptr(), hp, wp, int(pads[0]), int(pads[1]), probs[j].data_ptr(),
+                                             stream), "softmax3_hwc")
+        return probs
+
+    def _postprocess_group(self, pred, dst, pads):
+        """Post-processing of a group's n frames, enqueued on the current stream; their masks go into the first n frames
+        of ``dst`` ([>= n, H, W] int16 storage, pinned host memory or device).  ``pred``: distance models (border, cell),
+        each [n, Hp, Wp] with the top / left ``pads`` still on; boundary models the frames' (H, W, 3) softmax
+        probabilities one after the other (any iterable: a generator's softmax is enqueued right before the flood group
+        that needs it), whose floods share a launch in groups of at most 8.  Returns the tensors that must stay alive
+        until the current stream has passed this work."""
+        if self.model_settings['label_type'] == 'distance':
+            border, cell = pred
+            # every reference caller hands (H, W, 1) arrays to distance_postprocessing -> column-major instance ids
+            labels, _, _ = pp.distance_postprocessing_batch_device(border, cell, th_seed=self.ths[1], th_cell=self.ths[0],
+                                                                   pads=pads, col_major_ids=True)
+            dst[:labels.shape[0]].copy_(labels, non_blocking=True)
+            return [border, cell, labels]
+        keep, frames = [], iter(pred)
+        for c0 in itertools.count(0, 8):
+            probs = list(itertools.islice(frames, 8))
+            if not probs:
+                return keep
+            outs = pp.boundary_postprocessing_batch_device(probs, first_slot=0)
+            for i, (labels, _, _) in enumerate(outs):
+                dst[c0 + i].copy_(labels, non_blocking=True)
+            keep += [probs, outs]
+
+    def _device_frames(self, frames, clahe):
+        """[n, H, W] host frames -> (raw, minmax) on the device as ``tta.expand`` / ``resample.frames`` take them.  uint8 /
+        uint16: uploaded raw (CLAHE first if asked for: uint16 from there on), minmax (n, 2) int32 reduced on the device;
+        other dtypes: normalised per frame on the host as inference() does, float32, minmax None"""
+        if frames.dtype in (np.uint8, np.uint16):
+            n, H, W = frames.shape
+            host = np.ascontiguousarray(frames)
+            raw = torch.from_numpy(host.view(np.int16) if host.dtype == np.uint16 else host).to(self.device)
+            if clahe:                                            # on the frames as recorded
+                from ..utils.clahe import clahe_device
+                raw = clahe_device(raw)
+            minmax = torch.empty((n, 2), dtype=torch.int32, device=self.device)
+            _lib.check(_lib.load().mseg_frames_minmax(raw.data_ptr(), engine.RawFrame.PIX[raw.dtype], n, H * W,
+                                                      minmax.data_ptr(), torch.cuda.current_stream().cuda_stream),
+                       "frames_minmax")
+            return raw, minmax
+        xs = [normalize_host(frame, np.min(frame), np.max(frame)).astype(np.float32) for frame in frames]
+        return torch.from_numpy(np.ascontiguousarray(np.stack(xs))).to(self.device), None
+
+    def _zero_failed(self, pred, failed):
+        """zeros for the frames of a group's prediction (a tensor or a tuple of tensors, frames first) that did not fit"""
+        if any(failed):
+            bad = torch.tensor(failed, device=self.device)
+            for t in (pred if isinstance(pred, tuple) else (pred,)):
+                t[bad] = 0
+
     def _normalized_padded(self, frame):
         """one host frame -> (padded frame normalised with its own extrema, fp32, as inference() gets it; pads)"""
         frame_min, frame_max = np.min(frame), np.max(frame)
         padded, pads = self.pad_frame(np.copy(frame), frame_min)
-        return 2 * (padded.astype(np.float32) - frame_min) / (frame_max - frame_min) - 1, pads
+        return normalize_host(padded, frame_min, frame_max), pads
 
     def _group_input(self, frames):
         """[n, H, W] host frames -> (network input (n, 1, Hp, Wp) fp32 on the device, pads).  uint8 / uint16: uploaded raw,
@@ -327,29 +403,14 @@ class InferWorker(QObject):
             raise RuntimeError("predict_merged: a [n, H, W] array expected")
         n, H, W = (int(v) for v in frames.shape)
         boundary = self.model_settings['label_type'] == 'boundary'
-        lib = _lib.load()
         self.net.eval()
         with torch.cuda.device(self.device), torch.no_grad():
-            stream = torch.cuda.current_stream().cuda_stream
             if frames.dtype in (np.uint8, np.uint16):
                 pad_amounts((H, W))                              # frames beyond 8192 raise here, like every whole-frame route
-                host = np.ascontiguousarray(frames)
-                raw = torch.from_numpy(host.view(np.int16) if host.dtype == np.uint16 else host).to(self.device)
-                if clahe:                                        # on the un-transformed frames; uint16 from here on
-                    from ..utils.clahe import clahe_device
-                    raw = clahe_device(raw)
-                minmax = torch.empty((n, 2), dtype=torch.int32, device=self.device)
-                _lib.check(lib.mseg_frames_minmax(raw.data_ptr(), engine.RawFrame.PIX[raw.dtype], n, H * W,
-                                                  minmax.data_ptr(), stream), "frames_minmax")
-            else:                                                # normalised un-padded on the host, as inference() does
-                xs = []
-                for frame in frames:
-                    fmin, fmax = np.min(frame), np.max(frame)
-                    xs.append((2 * (frame.astype(np.float32) - fmin) / (fmax - fmin) - 1).astype(np.float32))
-                raw, minmax = torch.from_numpy(np.ascontiguousarray(np.stack(xs))).to(self.device), None
+            raw, minmax = self._device_frames(frames, clahe)     # (CLAHE on the un-transformed frames)
             failed = [False] * n
             members, keep = {}, []
-            for cs, (hm, wm), pads in T.shape_classes(codes, H, W):
+            for cs, _, pads in T.shape_classes(codes, H, W):
                 x = T.expand(raw, cs, pads, minmax)
                 hp, wp = int(x.shape[2]), int(x.shape[3])
                 x = x.view(len(cs) * n, 1, hp, wp)
@@ -361,10 +422,7 @@ class InferWorker(QObject):
                 pred = self._tta_join(pieces, n, failed, 3 if boundary else 1, hp, wp)
                 if boundary:
                     logits = pred.contiguous()
-                    probs = torch.empty((len(cs) * n, hm, wm, 3), dtype=torch.float32, device=self.device)
-                    for j in range(len(cs) * n):
-                        _lib.check(lib.mseg_softmax3_hwc(logits[j].data_ptr(), hp, wp, pads[0], pads[1],
-                                                         probs[j].data_ptr(), stream), "softmax3_hwc")
+                    probs = self._softmax_group(logits, pads)
                     keep += [logits, probs]
                     for ci, code in enumerate(cs):
                         members[code] = T.member(probs.permute(0, 3, 1, 2), code, first=ci * n)
@@ -378,10 +436,7 @@ class InferWorker(QObject):
             else:
                 merged = tuple(T.merge([members[c][h] for c in order], n, 1, H, W)[:, 0] for h in (0, 1))
             del keep                                             # (alive until the merges were enqueued on this stream)
-            if any(failed):
-                bad = torch.tensor(failed, device=self.device)
-                for t in (merged if isinstance(merged, tuple) else (merged,)):
-                    t[bad] = 0
+            self._zero_failed(merged, failed)
         return merged, failed
 
     def _tta_join(self, pieces, n, failed, ch, hp, wp):
@@ -403,21 +458,16 @@ class InferWorker(QObject):
         joined = tuple(torch.cat(p, dim=0) for p in parts)
         return joined[0] if heads == 1 else joined
 
-    def _infer_stack_tta(self, img):
-        """infer_stack with ``tta > 1``: group after group on the main stream — upload, expand, one forward per shape
-        class (and chunk), merge, hook, the batched post-processing, masks back through one pinned buffer.  No side
-        streams: nothing of a group overlaps the next one."""
-        from ..utils.utils import pad_amounts
-        from . import tta as T
-        codes = self._tta_member_codes()
+    def _infer_stack_groups(self, img, group, predict):
+        """infer_stack in groups of at most ``group`` frames, group after group on the main stream: ``predict(frames,
+        clahe)`` -> (the group's prediction without padding, at the frames' resolution — distance models (border, cell),
+        each (n, H, W); boundary models probabilities (n, H, W, 3) —, [frame failed?]), hook, the batched
+        post-processing, masks back through one pinned buffer.  No side streams: nothing of a group overlaps the next.
+        ``img`` holds at least one frame."""
         T_, H, W = (int(v) for v in img.shape)
         results = np.zeros(shape=(T_, H, W), dtype=np.uint16)
-        if T_ == 0:
-            return results
         boundary = self.model_settings['label_type'] == 'boundary'
         clahe = self._clahe_enabled(img)
-        pads = pad_amounts((H, W))
-        _, group = T.chunk_members(H + pads[0], W + pads[1], self.frame_batch, len(codes))
         group = min(group, T_)
         with torch.cuda.device(self.device), torch.no_grad():
             host = torch.empty((group, H, W), dtype=torch.int16, pin_memory=True)
@@ -425,8 +475,8 @@ class InferWorker(QObject):
                 if self.stop_inference:
                     break
                 n = min(group, T_ - f0)
-                pred, failed = self._predict_merged(img[f0:f0 + n], clahe)
-                if self.prediction_hook is not None:      # once per frame, in frame order, on the merged prediction
+                pred, failed = predict(img[f0:f0 + n], clahe)
+                if self.prediction_hook is not None:      # once per frame, in frame order, on the frame's own prediction
                     def hook(p, i):                       # (a frame that did not fit has no prediction: zero mask, no call)
                         return p if failed[i] else self.prediction_hook(p)
                     if boundary:
@@ -435,16 +485,7 @@ class InferWorker(QObject):
                     else:
                         hooked = [hook((pred[0][i:i + 1, None], pred[1][i:i + 1, None]), i) for i in range(n)]
                         pred = (torch.cat([h[0] for h in hooked], dim=0)[:, 0], torch.cat([h[1] for h in hooked], dim=0)[:, 0])
-                if boundary:
-                    for c0 in range(0, n, 8):
-                        outs = pp.boundary_postprocessing_batch_device([pred[i] for i in range(c0, min(c0 + 8, n))])
-                        for i, (labels, _, _) in enumerate(outs):
-                            host[c0 + i].copy_(labels, non_blocking=True)
-                else:
-                    labels, _, _ = pp.distance_postprocessing_batch_device(pred[0], pred[1], th_seed=self.ths[1],
-                                                                           th_cell=self.ths[0], pads=(0, 0),
-                                                                           col_major_ids=True)
-                    host[:n].copy_(labels, non_blocking=True)
+                self._postprocess_group(pred, host, (0, 0))
                 torch.cuda.current_stream().synchronize()
                 results[f0:f0 + n] = host[:n].numpy().view(np.uint16)
                 for i in range(n):
@@ -452,6 +493,18 @@ class InferWorker(QObject):
                         results[f0 + i] = 0
                     self.progress.emit(int(100 * (f0 + i + 1) / T_))
         return results
+
+    def _infer_stack_tta(self, img):
+        """infer_stack with ``tta > 1``: _infer_stack_groups over predict_merged (upload, expand, one forward per shape
+        class and chunk, merge)"""
+        from ..utils.utils import pad_amounts
+        from . import tta as T
+        codes = self._tta_member_codes()
+        if len(img) == 0:
+            return np.zeros(img.shape, dtype=np.uint16)
+        pads = pad_amounts(img.shape[1:])
+        _, group = T.chunk_members(img.shape[1] + pads[0], img.shape[2] + pads[1], self.frame_batch, len(codes))
+        return self._infer_stack_groups(img, group, self._predict_merged)
 
     # -- [extension] inference at a chosen resolution (inference/resample.py; DESIGN.md 6n) ------------------------------
     def _scale_checked(self):
@@ -495,92 +548,31 @@ class InferWorker(QObject):
             raise RuntimeError("predict_scaled: a [n, H, W] array expected")
         n, H, W = (int(v) for v in frames.shape)
         boundary = self.model_settings['label_type'] == 'boundary'
-        lib = _lib.load()
         self.net.eval()
         with torch.cuda.device(self.device), torch.no_grad():
-            (hs, ws), pads, ydown, xdown, yup, xup = self._scaled_geometry(H, W, s)
-            stream = torch.cuda.current_stream().cuda_stream
-            if frames.dtype in (np.uint8, np.uint16):
-                host = np.ascontiguousarray(frames)
-                raw = torch.from_numpy(host.view(np.int16) if host.dtype == np.uint16 else host).to(self.device)
-                if clahe:                                        # on the frames as recorded; uint16 from here on
-                    from ..utils.clahe import clahe_device
-                    raw = clahe_device(raw)
-                minmax = torch.empty((n, 2), dtype=torch.int32, device=self.device)
-                _lib.check(lib.mseg_frames_minmax(raw.data_ptr(), engine.RawFrame.PIX[raw.dtype], n, H * W,
-                                                  minmax.data_ptr(), stream), "frames_minmax")
-            else:                                                # normalised un-padded on the host, as inference() does
-                xs = []
-                for frame in frames:
-                    fmin, fmax = np.min(frame), np.max(frame)
-                    xs.append((2 * (frame.astype(np.float32) - fmin) / (fmax - fmin) - 1).astype(np.float32))
-                raw, minmax = torch.from_numpy(np.ascontiguousarray(np.stack(xs))).to(self.device), None
+            _, pads, ydown, xdown, yup, xup = self._scaled_geometry(H, W, s)
+            raw, minmax = self._device_frames(frames, clahe)
             x = R.frames(raw, ydown, xdown, pads, minmax)
             hp, wp = int(x.shape[1]), int(x.shape[2])
             chunks, _ = self._forward_group(x.view(n, 1, hp, wp))
             failed = [False] * n
             pred = self._tta_join(chunks, n, failed, 3 if boundary else 1, hp, wp)
             if boundary:
-                logits = pred.contiguous()
-                probs = torch.empty((n, hs, ws, 3), dtype=torch.float32, device=self.device)
-                for j in range(n):
-                    _lib.check(lib.mseg_softmax3_hwc(logits[j].data_ptr(), hp, wp, pads[0], pads[1], probs[j].data_ptr(),
-                                                     stream), "softmax3_hwc")
-                out = R.planes(probs.permute(0, 3, 1, 2), yup, xup, hwc=True)
+                out = R.planes(self._softmax_group(pred.contiguous(), pads).permute(0, 3, 1, 2), yup, xup, hwc=True)
             else:
                 out = tuple(R.planes(t, yup, xup, pads=pads)[:, 0] for t in pred)
-            if any(failed):
-                bad = torch.tensor(failed, device=self.device)
-                for t in (out if isinstance(out, tuple) else (out,)):
-                    t[bad] = 0
+            self._zero_failed(out, failed)
         return out, failed
 
     def _infer_stack_scaled(self, img):
-        """infer_stack with ``scale != 1``: group after group on the main stream — upload, resample, one forward, resample
-        back, hook, the batched post-processing at the frame's resolution, masks back through one pinned buffer.  No side
-        streams: nothing of a group overlaps the next one."""
+        """infer_stack with ``scale != 1``: _infer_stack_groups over predict_scaled (upload, resample, one forward,
+        resample back), so the post-processing runs at the frame's resolution"""
         s = self._scale_checked()
-        T_, H, W = (int(v) for v in img.shape)
-        results = np.zeros(shape=(T_, H, W), dtype=np.uint16)
-        if T_ == 0:
-            return results
-        boundary = self.model_settings['label_type'] == 'boundary'
-        clahe = self._clahe_enabled(img)
-        (hs, ws), pads = self._scaled_geometry(H, W, s)[:2]
-        group = min(frame_batch_for(hs + pads[0], ws + pads[1], self.frame_batch), T_)
-        with torch.cuda.device(self.device), torch.no_grad():
-            host = torch.empty((group, H, W), dtype=torch.int16, pin_memory=True)
-            for f0 in range(0, T_, group):
-                if self.stop_inference:
-                    break
-                n = min(group, T_ - f0)
-                pred, failed = self._predict_scaled(img[f0:f0 + n], clahe)
-                if self.prediction_hook is not None:      # once per frame, in frame order, on the full-resolution prediction
-                    def hook(p, i):                       # (a frame that did not fit has no prediction: zero mask, no call)
-                        return p if failed[i] else self.prediction_hook(p)
-                    if boundary:
-                        pred = torch.cat([hook(pred[i:i + 1].permute(0, 3, 1, 2), i).permute(0, 2, 3, 1)
-                                          for i in range(n)], dim=0).contiguous()
-                    else:
-                        hooked = [hook((pred[0][i:i + 1, None], pred[1][i:i + 1, None]), i) for i in range(n)]
-                        pred = (torch.cat([h[0] for h in hooked], dim=0)[:, 0], torch.cat([h[1] for h in hooked], dim=0)[:, 0])
-                if boundary:
-                    for c0 in range(0, n, 8):
-                        outs = pp.boundary_postprocessing_batch_device([pred[i] for i in range(c0, min(c0 + 8, n))])
-                        for i, (labels, _, _) in enumerate(outs):
-                            host[c0 + i].copy_(labels, non_blocking=True)
-                else:
-                    labels, _, _ = pp.distance_postprocessing_batch_device(pred[0], pred[1], th_seed=self.ths[1],
-                                                                           th_cell=self.ths[0], pads=(0, 0),
-                                                                           col_major_ids=True)
-                    host[:n].copy_(labels, non_blocking=True)
-                torch.cuda.current_stream().synchronize()
-                results[f0:f0 + n] = host[:n].numpy().view(np.uint16)
-                for i in range(n):
-                    if failed[i]:
-                        results[f0 + i] = 0
-                    self.progress.emit(int(100 * (f0 + i + 1) / T_))
-        return results
+        if len(img) == 0:
+            return np.zeros(img.shape, dtype=np.uint16)
+        (hs, ws), pads = self._scaled_geometry(int(img.shape[1]), int(img.shape[2]), s)[:2]
+        group = frame_batch_for(hs + pads[0], ws + pads[1], self.frame_batch)
+        return self._infer_stack_groups(img, group, self._predict_scaled)
 
     def _clahe_enabled(self, img):
         """apply_clahe for this stack?  Float stacks are segmented without it (no fixed grey-level range), with a message"""
@@ -626,12 +618,8 @@ class InferWorker(QObject):
                 self.progress.emit(int(100 * (f + 1) / T))
 
         def launch_postproc(f0, n, pred):
-            if self.prediction_hook is not None:      # once per frame, in frame order, on that frame's (1, C, Hp, Wp) slice
-                if boundary:
-                    pred = torch.cat([self.prediction_hook(pred[i:i + 1]) for i in range(n)], dim=0)
-                else:
-                    hooked = [self.prediction_hook((pred[0][i:i + 1], pred[1][i:i + 1])) for i in range(n)]
-                    pred = (torch.cat([h[0] for h in hooked], dim=0), torch.cat([h[1] for h in hooked], dim=0))
+            if self.prediction_hook is not None:
+                pred = hook_per_frame(self.prediction_hook, pred)
             ready = torch.cuda.Event()
             ready.record()
             host = free_hosts.pop() if free_hosts else torch.empty((group_cap, H, W), dtype=torch.int16, pin_memory=True)
@@ -639,20 +627,10 @@ class InferWorker(QObject):
                 side.wait_event(ready)
                 if boundary:
                     logits = pred.contiguous()
-                    keep = [logits]
-                    for c0 in range(0, n, 8):
-                        probs = [self._softmax_hwc(logits[i:i + 1], pads) for i in range(c0, min(c0 + 8, n))]
-                        outs = pp.boundary_postprocessing_batch_device(probs, first_slot=0)
-                        for i, (labels, _, _) in enumerate(outs):
-                            host[c0 + i].copy_(labels, non_blocking=True)
-                        keep += [probs, outs]
+                    keep = [logits] + self._postprocess_group((self._softmax_hwc(logits[i:i + 1], pads) for i in range(n)),
+                                                              host, pads)
                 else:
-                    border, cell = pred
-                    labels, _, _ = pp.distance_postprocessing_batch_device(border[:, 0], cell[:, 0], th_seed=self.ths[1],
-                                                                           th_cell=self.ths[0], pads=pads,
-                                                                           col_major_ids=True)
-                    host[:n].copy_(labels, non_blocking=True)
-                    keep = [border, cell, labels]
+                    keep = self._postprocess_group((pred[0][:, 0], pred[1][:, 0]), host, pads)
                 done = torch.cuda.Event()
                 done.record(side)
             pending.append((f0, n, host, done, keep))
@@ -866,7 +844,7 @@ class InferWorker(QObject):
                     img_frame = self._clahe_host_frame(img[frame]) if clahe else np.copy(img[frame])
                     frame_min, frame_max = np.min(img_frame), np.max(img_frame)
                     img_frame, pads = self.pad_frame(img_frame, frame_min)
-                    img_batch = 2 * (img_frame.astype(np.float32) - frame_min) / (frame_max - frame_min) - 1
+                    img_batch = normalize_host(img_frame, frame_min, frame_max)
                     img_batch = torch.from_numpy(np.ascontiguousarray(img_batch[None, None, :, :])).to(torch.float)
                     pred = self._forward(img_batch)
                 if pred is None:                 # out of memory: zero mask, like inference() (infer.py:354-356)

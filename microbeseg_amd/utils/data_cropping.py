@@ -193,9 +193,10 @@ class DataCropWorker(QObject):
 
         :return: instance mask, np.uint16, shape of the crop
         """
+        from ..inference.infer import normalize_host
         worker = self._require_model()
         crop = np.asarray(crop)
-        img_batch = 2 * (crop.astype(np.float32) - min_val) / (max_val - min_val) - 1
+        img_batch = normalize_host(crop, min_val, max_val)
         x = torch.from_numpy(np.ascontiguousarray(img_batch[None, None, :, :])).to(torch.float)
         with torch.cuda.device(self.device), torch.no_grad():
             masks = self._predict(worker, x.to(self.device), shape_errors_too=True)
@@ -205,6 +206,8 @@ class DataCropWorker(QObject):
         if self._infer is None:
             raise RuntimeError("pre-labelling needs a model: DataCropWorker(..., pre_labeling=True, model=<path>)")
         self._infer.precision = self.precision
+        if self.ths is not None:                     # (distance models: the thresholds its post-processing step reads)
+            self._infer.ths = self.ths
         self._infer.net.eval()
         return self._infer
 
@@ -214,9 +217,11 @@ class DataCropWorker(QObject):
 
     def _predict(self, worker, x, cap=None, shape_errors_too=False):
         """(n, 1, S, S) network input on the device -> int16-storage uint16 masks (n, S, S) on the device.  One forward for
-        all n (at most ``cap[0]`` per forward once an out-of-memory halved the group: InferWorker._forward_group), one
-        batched post-processing call per forward for distance models, softmax + flood groups of 8 for boundary models."""
-        from ..inference import postprocessing as pp
+        all n (at most ``cap[0]`` per forward once an out-of-memory halved the group: InferWorker._forward_group), the
+        hook per crop and one InferWorker._postprocess_group per forward.  ``worker`` comes from ``_require_model``, which
+        has set its precision and, for distance models, its thresholds to this object's: the post-processing step reads
+        ``worker.ths``, not ``self.ths``."""
+        from ..inference.infer import hook_per_frame
         n, _, S, _ = x.shape
         boundary = self.model_settings['label_type'] != 'distance'
         masks = torch.zeros((n, S, S), dtype=torch.int16, device=x.device)
@@ -236,23 +241,13 @@ class DataCropWorker(QObject):
                 if pred is None:                                  # zero masks, message already sent
                     continue
                 if self.prediction_hook is not None:
-                    if boundary:
-                        pred = torch.cat([self.prediction_hook(pred[j:j + 1]) for j in range(cm)], dim=0)
-                    else:
-                        hooked = [self.prediction_hook((pred[0][j:j + 1], pred[1][j:j + 1])) for j in range(cm)]
-                        pred = (torch.cat([h[0] for h in hooked], dim=0), torch.cat([h[1] for h in hooked], dim=0))
-                dst = masks[i + c0:i + c0 + cm]
+                    pred = hook_per_frame(self.prediction_hook, pred)
                 if boundary:
                     logits = pred.contiguous()
-                    for g0 in range(0, cm, 8):
-                        probs = [worker._softmax_hwc(logits[j:j + 1], (0, 0)) for j in range(g0, min(g0 + 8, cm))]
-                        for j, (labels, _, _) in enumerate(pp.boundary_postprocessing_batch_device(probs)):
-                            dst[g0 + j].copy_(labels)
+                    pred = (worker._softmax_hwc(logits[j:j + 1], (0, 0)) for j in range(cm))
                 else:
-                    border, cell = pred
-                    labels, _, _ = pp.distance_postprocessing_batch_device(border[:, 0], cell[:, 0], th_seed=self.ths[1],
-                                                                           th_cell=self.ths[0], col_major_ids=True)
-                    dst.copy_(labels)
+                    pred = (pred[0][:, 0], pred[1][:, 0])
+                worker._postprocess_group(pred, masks[i + c0:i + c0 + cm], (0, 0))
             i += m
         return masks
 
@@ -382,6 +377,7 @@ class DataCropWorker(QObject):
     @staticmethod
     def _extract_host(frame, origins, S, vmin, vmax, pre, dev):
         """frames of other dtypes than uint8 / uint16: the reference's formulas on the host (like InferWorker._group_input)"""
+        from ..inference.infer import normalize_host
         y_pads, x_pads = max(0, S - frame.shape[0]), max(0, S - frame.shape[1])
         img = np.pad(frame, ((0, y_pads), (0, x_pads)), mode='constant', constant_values=vmin)
         raws, shows, xs = [], [], []
@@ -389,7 +385,7 @@ class DataCropWorker(QObject):
             crop = img[a:a + S, b:b + S]
             raws.append(crop)
             shows.append((255 * (crop.astype(np.float32) - vmin) / (vmax - vmin)).astype(np.uint8))
-            xs.append(2 * (crop.astype(np.float32) - vmin) / (vmax - vmin) - 1)
+            xs.append(normalize_host(crop, vmin, vmax))
         out = {"raw_host": np.stack(raws), "show_host": np.stack(shows)}
         out["show"] = torch.from_numpy(out["show_host"]).to(dev)
         if pre:

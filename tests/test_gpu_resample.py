@@ -447,6 +447,52 @@ def test_masks_without_a_hook_inference_and_clahe(tmp_path, dev):
     assert enhanced.shape == (T, H, W) and enhanced.dtype == np.uint16
 
 
+def _halving(n, limit):
+    """batch sizes InferWorker._forward_group asks of the network for a group of n frames when more than ``limit`` samples
+    do not fit: a forward that fails is retried at half its size (at least 1) from the same frame on, and that size is kept
+    for the rest of the group; a single frame that does not fit is given up"""
+    asked, i, size = [], 0, n
+    while i < n:
+        m = min(size, n - i)
+        asked.append(m)
+        if m > limit and m > 1:
+            size = max(1, m // 2)
+            continue
+        i += m
+    return asked
+
+
+def test_groups_that_do_not_fit_in_memory(tmp_path, dev):
+    """a group whose forward runs out of memory is halved down to what fits and the masks stay the same; a frame that does
+    not fit alone gets the zero mask and no hook call, like the routes at scale 1"""
+    worker = _worker(tmp_path, "DU")
+    worker.scale, worker.frame_batch = 0.5, 2
+    T, H, W = 4, 128, 128
+    rng = np.random.Generator(np.random.PCG64(14))
+    stack = rng.integers(0, 60000, size=(T, H, W)).astype(np.uint16)
+    hook, calls = _distance_hook(T, H, W, dev, seed=7)
+    worker.prediction_hook = hook
+    want = worker.infer_stack(stack)
+    assert calls == list(range(T)) and int(want.max()) > 5
+    forward, asked, limit = worker.net.forward, [], [1]
+
+    def short_of_memory(x):
+        asked.append(int(x.shape[0]))
+        if x.shape[0] > limit[0]:
+            raise RuntimeError("HIP out of memory. Tried to allocate 1.00 GiB")
+        return forward(x)
+    worker.net.forward = short_of_memory
+    del calls[:]
+    got = worker.infer_stack(stack)
+    assert asked == _halving(2, 1) * 2 == [2, 1, 1] * 2, asked          # every group starts at frame_batch again
+    assert calls == list(range(T)) and np.array_equal(got, want)
+    limit[0] = 0
+    del calls[:], asked[:]
+    got = worker.infer_stack(stack)
+    assert asked == _halving(2, 0) * 2 == [2, 1, 1] * 2, asked
+    assert not calls and got.shape == (T, H, W) and got.dtype == np.uint16 and not got.any()
+
+
 def test_scale_1_is_untouched_and_combinations_are_refused_before_any_launch(tmp_path, dev, monkeypatch):
     from microbeseg_amd import _lib
     worker = _worker(tmp_path, "DU")
