@@ -732,6 +732,36 @@ int mseg_cell_order_stats(const void* labels, int label_dtype, int T, int H, int
                           const int64_t* bg_ranks, uint32_t* values, uint32_t* bg_values, int32_t* status, void* ws,
                           size_t ws_bytes, void* stream);
 
+/* ---- per-cell intensity profile along the cell axis (csrc/profile.hip) — an extension ----------------------
+ * labels, label_dtype, label_off, img, img_dtype, C and the four element strides as for mseg_cell_order_stats: the image is
+ * uint8 or uint16 and is read in place, whatever its strides.  bbox is the device array mseg_cell_measure writes
+ * ([n_labels][4] = r0, c0, r1, c1, half-open, zeros for an absent cell).  dir: int32 [n_labels][2] on the device = (uy, ux),
+ * the cell's direction in (row, column); the caller makes it (floor(16384 cos o + 0.5), floor(16384 sin o + 0.5) for an
+ * orientation o), the device never sees a float of it.  2 <= N <= 32, 1 <= C <= 8.  For cell s, over its pixels (y, x) inside
+ * its box (clipped to the frame):
+ *     q      = uy y + ux x                                   in int64
+ *     qmin, qmax = the extremes of q
+ *     b      = floor((q - qmin) N / (qmax - qmin + 1))       exact, then clamped to 0 .. N - 1 (exact arithmetic never leaves
+ *                                                            that range; the clamp keeps any dir inside the arrays)
+ * mseg_cell_profile: outputs, written whole, integers only, identical bytes from run to run:
+ *     count   uint32 [N][n_labels]     count[b][s]   = the pixels of cell s in bin b
+ *     sums    uint64 [C][N][n_labels]  sums[c][b][s] = the sum of their channel-c values (exact: < 2^31 * 65535)
+ *     extent  int64  [2][n_labels]     qmin, qmax
+ *   Bin 0 is the end with the smaller projection.  A one-pixel cell, and a cell whose pixels share one q, lie in bin 0.
+ *   Pixels of other cells and background inside the box, ids beyond the frame's table and negative ids do not count.  An
+ *   absent cell (an all-zero box), and a box that holds no pixel of its cell, get zeros everywhere.  b is exact while
+ *   (qmax - qmin + 1) N < 2^63, which holds for every |uy|, |ux| <= 2^20 (H W < 2^31): an fp32 estimate of the quotient,
+ *   corrected by the 64-bit remainder.
+ *   There is no status word: a box that does not cover its cell shows as sum_b count[b][s] != the cell's area, which the
+ *   caller checks.  No read or write ever leaves the arrays as sized here.
+ *   One wave per cell slot, two walks over the box (the extremes by a wave reduction, then the bins in LDS), plain stores;
+ *   no global atomics, no workspace.  MSEG_EINVAL: bad sizes, N or C out of range, a dtype not listed, H * W >= 2^31 - 512;
+ *   nothing is launched and nothing written.  n_labels == 0: nothing to do (bbox, dir and the outputs may be NULL).        */
+int mseg_cell_profile(const void* labels, int label_dtype, int T, int H, int W, const int64_t* label_off, int64_t n_labels,
+                      const void* img, int img_dtype, int C, int64_t frame_stride, int64_t chan_stride, int64_t row_stride,
+                      int64_t pix_stride, const int32_t* bbox, const int32_t* dir, int N, uint32_t* count, uint64_t* sums,
+                      int64_t* extent, void* stream);
+
 /* ---- per-cell neighbourhood (csrc/neighbors.hip) — an extension ------------------------------------------
  * labels, dtype and label_off as for mseg_cell_links: cell l of frame t has slot label_off[t] + l - 1; ids beyond the frame's
  * table and negative ids are not a cell, neither as a pixel nor as a neighbour: they count as background.  H * W < 2^31 - 512.

@@ -18,6 +18,7 @@ the GUI's Export button (inference/result_export.py) for the segmented channel o
 ``--percentiles [P ...]`` with ``--cells``: percentiles (default 50, the median) of every cell's pixel values and of the background;
 ``--neighbors [R]`` with ``--cells``: every cell's contacts and nearest neighbour within R pixels, and ``..._contacts.csv``, the pairs;
 ``--spots THR [--spot_scale S]`` with ``--cells``: every cell's fluorescent foci of at least THR grey levels, and ``..._spots.csv``, the spots.
+``--profile [N]`` with ``--cells``: every cell's intensity profile along its axis in N bins (default 16), and ``..._profiles.csv``, the profiles.
 """
 import argparse
 from pathlib import Path
@@ -129,6 +130,14 @@ class Parser(argparse.ArgumentParser):
                 ns.spots, ns.spot_scale = check_spots(ns.spots, ns.spot_scale)
             except ValueError as e:
                 self.error(f'--spots: {e}')
+        if ns.profile is not None:
+            if not ns.cells:
+                self.error('--profile needs --cells (it adds columns to the cell table)')
+            from microbeseg_amd.inference.cells import check_profile
+            try:
+                ns.profile = check_profile(ns.profile)
+            except ValueError as e:
+                self.error(f'--profile: {e}')
         if ns.scale != 1:
             if ns.tta > 1:
                 self.error('--scale and --tta > 1 cannot be combined')
@@ -259,6 +268,17 @@ def build_parser():
     parser.add_argument('--spot_scale', default=2, type=int, metavar='S',
                         help='[extension] with --spots: the size of the foci, 1 .. 5 (default 2): the band-pass is the '
                              'difference of Gaussians with sigma = sqrt(S / 2) and sqrt(S) pixels')
+    parser.add_argument('--profile', nargs='?', const=16, default=None, type=int, metavar='N',
+                        help='[extension] with --cells: add where along the cell the signal of every measured channel sits, for '
+                             'signals that form no foci (a polar cap, a septal band, a gradient).  Every cell\'s pixels are '
+                             'projected on its orientation and the projected extent is cut into N bins from pole to pole '
+                             '(default N = 16, 2 <= N <= 32), on the device; the table gains axis_extent (the pole-to-pole '
+                             'length in pixels), pole_mid_ratio_ch{c} (mean of the outer quarters over the mean of the rest), '
+                             'pole_asym_ch{c} (0 = both poles alike, 1 = all at one pole) and profile_peak_ch{c} (the centre of '
+                             'the brightest bin, -1 .. 1; the sign is arbitrary); also write <mask file stem>_profiles.csv, one '
+                             'row per cell, channel and bin: frame, channel, label, bin, bin_pos, count, sum, mean.  Whole '
+                             'pixels, along the straight orientation axis: a bent cell is folded onto its chord; no '
+                             'background subtraction, no normalisation across cells, no demograph image; uint8 / uint16 images')
     return parser
 
 
@@ -309,6 +329,7 @@ def main():
     worker.neighbors = args.neighbors
     worker.spots = args.spots
     worker.spot_scale = args.spot_scale
+    worker.profile = args.profile
     worker.tta = args.tta
     worker.scale = args.scale
     if args.drift is not None:
@@ -331,6 +352,9 @@ def main():
     if args.spots is not None:
         print(f'Cell table: with the fluorescent foci of every cell (response >= {args.spots} grey levels at scale '
               f'{args.spot_scale}); the spots go to ..._spots.csv')
+    if args.profile is not None:
+        print(f'Cell table: with the intensity profile of every cell along its axis in {args.profile} bins; the profiles go '
+              'to ..._profiles.csv')
     if args.scale != 1:
         print(f'Inference at {args.scale} x the resolution of the frames')
     if args.tta > 1:
@@ -371,11 +395,15 @@ def main():
                 print(f'Skip intensity columns of {img_id.stem} (they need uint8 / uint16 images, got {view.dtype})')
                 view, channels = None, []
             worker.spots = args.spots if view is not None else None      # the spot columns are intensity columns
+            worker.profile = args.profile if view is not None else None  # so are the profile columns
             write_cells(worker.cell_table(results, view, channels), out_file.with_name(out_file.stem + '_cells.csv'))
             if args.neighbors is not None:
                 write_cells(worker.contact_table(results), out_file.with_name(out_file.stem + '_contacts.csv'))
             if worker.spots is not None:
                 write_cells(worker.spot_table(results, view, channels), out_file.with_name(out_file.stem + '_spots.csv'))
+            if worker.profile is not None:
+                write_cells(worker.profile_table(results, view, channels),
+                            out_file.with_name(out_file.stem + '_profiles.csv'))
     print('--- Finished ---')
 
 

@@ -197,6 +197,8 @@ SIGNATURES = {
     "mseg_cell_order_stats_workspace_bytes": (_SZ, [_I, C.c_int64, _I, _I]),
     "mseg_cell_order_stats": (_I, [_P, _I, _I, _I, _I, _P, C.c_int64, _P, _I, _I, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
                                    _P, _I, _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    "mseg_cell_profile": (_I, [_P, _I, _I, _I, _I, _P, C.c_int64, _P, _I, _I, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+                               _P, _P, _I, _P, _P, _P, _P]),
     "mseg_cell_neighbors_workspace_bytes": (_SZ, [_I, C.c_int64, C.c_int64]),
     "mseg_cell_neighbors": (_I, [_P, _I, _I, _I, _I, _P, C.c_int64, _I, C.c_int64, _P, _P, C.c_int64, _P, _P, _P, _SZ, _P]),
     "mseg_cell_spots_workspace_bytes": (_SZ, [_I, C.c_int64, _I]),

@@ -3,7 +3,7 @@
 set -e
 cd "$(dirname "$0")"
 OUT=../libmseg_hip.so
-SRCS="igemm.hip igemm_p8.hip wgrad.hip first.hip norm.hip head.hip loss.hip augment.hip clahe.hip labels.hip polygons.hip analysis.hip cells.hip hull.hip midline.hip order_stats.hip neighbors.hip spots.hip drift.hip prepare.hip resident.hip tta.hip resample.hip api_misc.hip"
+SRCS="igemm.hip igemm_p8.hip wgrad.hip first.hip norm.hip head.hip loss.hip augment.hip clahe.hip labels.hip polygons.hip analysis.hip cells.hip hull.hip midline.hip order_stats.hip profile.hip neighbors.hip spots.hip drift.hip prepare.hip resident.hip tta.hip resample.hip api_misc.hip"
 [ -f postproc.hip ] && SRCS="$SRCS postproc.hip"
 mkdir -p ../_build
 OBJS=""

@@ -1,6 +1,7 @@
-// cell_common.h — what the per-cell files share (cells, hull, midline, order_stats, neighbors, spots, drift):
-// the eight-pixel loader, the rule that makes an id a cell of its frame, the pair table's hash and slot claim, and the
-// opening checks and type dispatch of the entry points.  A new per-cell file takes these from here.
+// cell_common.h — what the per-cell files share (cells, hull, midline, order_stats, profile, neighbors, spots, drift;
+// DESIGN.md §6l): the eight-pixel loader, the rule that makes an id a cell of its frame, the walk of one wave over a cell's
+// box, the pair table's hash and slot claim, and the opening checks and type dispatch of the entry points.  A new per-cell
+// file takes these from here.
 #pragma once
 #include "common.h"
 
@@ -39,6 +40,52 @@ __device__ __forceinline__ void cell_load8(const E* __restrict__ base, int64_t q
 
 // an id is a cell of its frame only if the frame's table of K entries holds it; everything else is 0
 __device__ __forceinline__ int cell_id(int v, int64_t K) { return (v > 0 && (int64_t)v <= K) ? v : 0; }
+
+// ---- one wave per cell slot (order_stats, profile) ------------------------------------------------------------------------
+#define CELL_WAVE 64
+
+// the frame of slot s: the last t with loff[t] <= s
+__device__ __forceinline__ int cell_slot_frame(const int64_t* __restrict__ loff, int T, int64_t s) {
+  int lo_t = 0, hi_t = T;
+  while (hi_t - lo_t > 1) {
+    const int mid = (lo_t + hi_t) >> 1;
+    if (loff[mid] <= s) lo_t = mid; else hi_t = mid;
+  }
+  return lo_t;
+}
+
+// A cell's box (r0, c0, r1, c1, half-open), clipped to the frame: no read leaves the arrays, whatever the box says.  An
+// all-zero box (an absent cell) and a label that is no id have no elements.
+struct CellWalk {
+  int r0, c0, bw, cells;          // the first row and column, the width, the elements of the clipped box
+  int lbl;                        // the cell's id in its frame
+  int qy, qx;                     // 64 elements on in flat order: qy rows and qx columns
+};
+
+__device__ __forceinline__ CellWalk cell_walk_box(int4 bb, int H, int W, int64_t l64) {
+  CellWalk k;
+  k.r0 = max(bb.x, 0); k.c0 = max(bb.y, 0);
+  const int r1 = min(bb.z, H), c1 = min(bb.w, W);
+  k.bw = c1 > k.c0 ? c1 - k.c0 : 0;
+  const int bh = r1 > k.r0 ? r1 - k.r0 : 0;
+  k.cells = (l64 >= 1 && l64 <= 0x7FFFFFFFll) ? k.bw * bh : 0;              // bw * bh <= H * W < 2^31 - 512
+  k.lbl = (int)l64;
+  k.qy = k.bw ? CELL_WAVE / k.bw : 0; k.qx = k.bw ? CELL_WAVE % k.bw : 0;
+  return k;
+}
+
+// The wave walks the box in flat order (lane i takes element i, i + 64, ... of the box, so consecutive lanes take
+// consecutive columns and run on into the next row: a box narrower than the wave leaves no lane idle) and calls f(y, x)
+// for every pixel of the cell, in frame coordinates.
+template <typename L, typename F>
+__device__ __forceinline__ void cell_walk(const L* __restrict__ frame, int W, const CellWalk& k, int lane, F&& f) {
+  int y = k.bw ? lane / k.bw : 0, x = k.bw ? lane % k.bw : 0;
+  for (int i = lane; i < k.cells; i += CELL_WAVE) {
+    if ((int)frame[(int64_t)(k.r0 + y) * W + k.c0 + x] == k.lbl && (sizeof(L) == 4 || k.lbl <= 0xFFFF)) f(k.r0 + y, k.c0 + x);
+    y += k.qy; x += k.qx;
+    if (x >= k.bw) { x -= k.bw; ++y; }
+  }
+}
 
 __device__ __forceinline__ uint32_t cell_pair_hash(uint32_t a, uint32_t b) {
   uint32_t h = a * 0x9E3779B1u ^ b * 0x85EBCA77u;

@@ -78,8 +78,7 @@ __device__ __forceinline__ void os_spread(bool hit, int& bin, uint32_t& rem) {
 }
 
 // ---- a. cells: one wave per slot --------------------------------------------------------------------------------------------
-// The wave walks the cell's box in flat order (lane i takes element i, i + 64, ... of the box, so consecutive lanes take
-// consecutive columns and run on into the next row: a box narrower than the wave leaves no lane idle).
+// The wave walks the cell's box in flat order (cell_walk, cell_common.h).
 template <typename L, typename P>
 __global__ void __launch_bounds__(OS_WAVE) os_cell_kernel(const L* __restrict__ lab, int T, int H, int W,
                                                           const int64_t* __restrict__ loff, int64_t n,
@@ -98,20 +97,10 @@ __global__ void __launch_bounds__(OS_WAVE) os_cell_kernel(const L* __restrict__ 
     for (int e = lane; e < R * C; e += OS_WAVE) values[(int64_t)e * n + s] = 0;
     return;
   }
-  int lo_t = 0, hi_t = T;                                           // the frame: the last t with loff[t] <= s
-  while (hi_t - lo_t > 1) {
-    const int mid = (lo_t + hi_t) >> 1;
-    if (loff[mid] <= s) lo_t = mid; else hi_t = mid;
-  }
-  const int t = lo_t;
-  const int64_t l64 = s - loff[t] + 1;
-  // the box, clipped to the frame: no read leaves the arrays, whatever the box says.  A box that misses pixels of the
-  // cell shows as a rank beyond the pixels found.
-  const int r0 = max(bb.x, 0), c0 = max(bb.y, 0), r1 = min(bb.z, H), c1 = min(bb.w, W);
-  const int bw = c1 > c0 ? c1 - c0 : 0, bh = r1 > r0 ? r1 - r0 : 0;
-  const int cells = (l64 >= 1 && l64 <= 0x7FFFFFFFll) ? bw * bh : 0;       // bw * bh <= H * W < 2^31 - 512
-  const int lbl = (int)l64;
-  const int qy = bw ? OS_WAVE / bw : 0, qx = bw ? OS_WAVE % bw : 0;
+  const int t = cell_slot_frame(loff, T, s);
+  // the box, clipped to the frame (cell_common.h).  A box that misses pixels of the cell shows as a rank beyond the
+  // pixels found.
+  const CellWalk box = cell_walk_box(bb, H, W, s - loff[t] + 1);
   const L* frame = lab + (int64_t)t * H * W;
   bool bad = false;
   for (int c = 0; c < C; ++c) {
@@ -119,17 +108,10 @@ __global__ void __launch_bounds__(OS_WAVE) os_cell_kernel(const L* __restrict__ 
 #pragma unroll
     for (int k = 0; k < 4; ++k) hist[4 * lane + k] = 0;
     __syncthreads();
-    {
-      int y = bw ? lane / bw : 0, x = bw ? lane % bw : 0;
-      for (int i = lane; i < cells; i += OS_WAVE) {
-        if ((int)frame[(int64_t)(r0 + y) * W + c0 + x] == lbl && (sizeof(L) == 4 || lbl <= 0xFFFF)) {
-          const unsigned v = plane[(int64_t)(r0 + y) * rs + (int64_t)(c0 + x) * ps];
-          atomicAdd(&hist[WIDE ? v >> 8 : v], 1u);
-        }
-        y += qy; x += qx;
-        if (x >= bw) { x -= bw; ++y; }
-      }
-    }
+    cell_walk(frame, W, box, lane, [&](int y, int x) {
+      const unsigned v = plane[(int64_t)y * rs + (int64_t)x * ps];
+      atomicAdd(&hist[WIDE ? v >> 8 : v], 1u);
+    });
     __syncthreads();
     uint32_t cnt[4], excl, m;
 #pragma unroll
@@ -167,18 +149,11 @@ __global__ void __launch_bounds__(OS_WAVE) os_cell_kernel(const L* __restrict__ 
     __syncthreads();
     if (lane < R && my_bin >= 0 && my_slot == lane) hist[my_bin] = (uint32_t)lane;
     __syncthreads();
-    {
-      int y = bw ? lane / bw : 0, x = bw ? lane % bw : 0;
-      for (int i = lane; i < cells; i += OS_WAVE) {
-        if ((int)frame[(int64_t)(r0 + y) * W + c0 + x] == lbl && (sizeof(L) == 4 || lbl <= 0xFFFF)) {
-          const unsigned v = plane[(int64_t)(r0 + y) * rs + (int64_t)(c0 + x) * ps];
-          const uint32_t slot = hist[(v >> 8) & 0xFF];
-          if (slot < (uint32_t)OS_MAXR) atomicAdd(&low[slot * OS_BINS + (v & 0xFF)], 1u);
-        }
-        y += qy; x += qx;
-        if (x >= bw) { x -= bw; ++y; }
-      }
-    }
+    cell_walk(frame, W, box, lane, [&](int y, int x) {
+      const unsigned v = plane[(int64_t)y * rs + (int64_t)x * ps];
+      const uint32_t slot = hist[(v >> 8) & 0xFF];
+      if (slot < (uint32_t)OS_MAXR) atomicAdd(&low[slot * OS_BINS + (v & 0xFF)], 1u);
+    });
     __syncthreads();
     for (int j = 0; j < R; ++j) {
       const int bin = __shfl(my_bin, j, OS_WAVE), slot = __shfl(my_slot, j, OS_WAVE);

@@ -37,7 +37,12 @@ grey levels, counted under every cell and on the background (csrc/spots.hip: ``m
 ``cell_spots`` returns the spots themselves with their position along the cell's axes, which separates polar from mid-cell
 foci.  Integers from the device, one division per float here.  Whole pixels and a fixed threshold: no sub-pixel positions,
 no Gaussian fitting, no automatic or noise-relative threshold (the list carries the response: re-threshold afterwards), no
-float images, no linking of spots over time.
+float images, no linking of spots over time.  ``profile=N`` adds WHERE ALONG THE CELL the signal sits, for signals that form
+no foci: every cell's pixels are projected on its orientation, the projected extent is cut into N bins from pole to pole, and
+the device returns every bin's pixel count and channel sums (csrc/profile.hip: ``mseg_cell_profile``); the
+table gains the pole-to-pole extent, the pole / mid-cell ratio, the pole asymmetry and the position of the brightest bin,
+``cell_profiles`` returns the profiles themselves, one row per cell, channel and bin.  Whole pixels, along the straight
+orientation axis (a bent cell is folded onto its chord), no background subtraction, no normalisation across cells.
 """
 import ctypes as C
 import math
@@ -74,19 +79,24 @@ SPOT_COLUMNS = ['n_spots_ch{c}', 'spot_max_ch{c}', 'spot_sum_ch{c}', 'bg_spots_c
 SPOT_TABLE_COLUMNS = ['frame', 'channel', 'label', 'y', 'x', 'value', 'response', 'axis_pos', 'axis_off']
 MAX_SPOT_SCALE = 5    # largest scale mseg_cell_spots accepts
 MAX_SPOT_THRESHOLD = 65535
+PROFILE_COLUMNS = ['pole_mid_ratio_ch{c}', 'pole_asym_ch{c}', 'profile_peak_ch{c}']      # after axis_extent, channel by channel
+PROFILE_TABLE_COLUMNS = ['frame', 'channel', 'label', 'bin', 'bin_pos', 'count', 'sum', 'mean']
+MIN_PROFILE_BINS, MAX_PROFILE_BINS = 2, 32      # the bins mseg_cell_profile accepts
+MAX_PROFILE_CHANNELS = 8    # most channels of one mseg_cell_profile call
+PROFILE_UNIT = 16384        # the length of the integer direction (uy, ux) a profile is taken along
 SPOT_RECORD = np.dtype([('frame', '<i4'), ('channel', '<i4'), ('y', '<i4'), ('x', '<i4'), ('label', '<i4'), ('value', '<i4'),
                         ('d', '<i8')])      # MsegSpot
 
 
 def columns(channels=(), link=True, drift=False, hull=False, midline=False, percentiles=(), neighbors=False, spots=False,
-            flow=False, gap=False):
+            flow=False, gap=False, profile=False):
     """the table's columns, in order, for the measured ``channels``; ``drift``: with the drift columns (needs ``link``);
     ``flow``: with flow_y / flow_x after the drift columns (needs ``drift``); ``gap``: with pred_gap after the link, drift and
     flow columns (needs ``link``);
     ``hull``: with the outline columns; ``midline``: with the midline columns; ``percentiles``: with p{P}_ch{c} for every
     measured channel (per channel the percentiles in the order given), then bg_p{P}_ch{c} likewise; ``neighbors``: with the
-    neighbourhood columns; ``spots``: with the four spot columns of every measured channel, channel by channel; these come
-    last"""
+    neighbourhood columns; ``spots``: with the four spot columns of every measured channel, channel by channel; ``profile``:
+    with axis_extent and the three profile columns of every measured channel, channel by channel; these come last"""
     if drift and not link:
         raise ValueError("the drift columns belong to the link columns: drift needs link")
     if flow and not drift:
@@ -101,7 +111,8 @@ def columns(channels=(), link=True, drift=False, hull=False, midline=False, perc
         (list(HULL_COLUMNS) if hull else []) + (list(MIDLINE_COLUMNS) if midline else []) + \
         [name.format(p=int(q), c=int(c)) for name in (PERCENTILE_COLUMNS if percentiles else ()) for c in channels
          for q in percentiles] + (list(NEIGHBOR_COLUMNS) if neighbors else []) + \
-        [name.format(c=int(c)) for c in (channels if spots else ()) for name in SPOT_COLUMNS]
+        [name.format(c=int(c)) for c in (channels if spots else ()) for name in SPOT_COLUMNS] + \
+        ((['axis_extent'] + [name.format(c=int(c)) for c in channels for name in PROFILE_COLUMNS]) if profile else [])
 
 
 def _device(device=None):
@@ -1008,6 +1019,215 @@ def _spot_sums(records, off, n_channels):
     return {(k // n, k % n): (m, (h << 32) + l) for k, m, l, h in zip(keys.tolist(), top.tolist(), lo.tolist(), hi.tolist())}
 
 
+def check_profile(bins):
+    """the rule of ``measure_cells(profile=...)``, ``InferWorker.profile`` and --profile: None = off -> None; else a whole
+    number of bins in 2 .. 32 -> an int"""
+    if bins is None:
+        return None
+    try:
+        ok = not isinstance(bins, (bool, str, bytes)) and int(bins) == bins and \
+            MIN_PROFILE_BINS <= int(bins) <= MAX_PROFILE_BINS
+    except (TypeError, ValueError, OverflowError):
+        ok = False
+    if not ok:
+        raise ValueError(f"profile: None or a whole number of bins in {MIN_PROFILE_BINS} .. {MAX_PROFILE_BINS} expected, "
+                         f"got {bins!r}")
+    return int(bins)
+
+
+def profile_direction(orientation):
+    """The integer direction (uy, ux) in (row, column) a profile is taken along, for the table's ``orientation`` o (``_axes``,
+    the value ``spot_axes`` also projects on): uy = floor(16384 cos o + 0.5), ux = floor(16384 sin o + 0.5) -> int32 [n, 2].
+    Bin 0 of a profile is the end with the SMALLER projection uy y + ux x, the sense in which the spots' axis_pos grows;
+    the other sense would do as well, because a cell has no head.  The C library's cos / sin value by value, as in
+    ``spot_axes``; the device only ever sees the integers.  Pure host code."""
+    o = np.asarray(orientation, np.float64).reshape(-1)
+    out = np.zeros((len(o), 2), np.int32)
+    for i, v in enumerate(o.tolist()):
+        out[i] = math.floor(PROFILE_UNIT * math.cos(v) + 0.5), math.floor(PROFILE_UNIT * math.sin(v) + 0.5)
+    return out
+
+
+def _orientations(raw):
+    """the table's orientation (``_axes``) of every cell slot of ``measure_raw``'s sums -> (fp64 [n], present bool [n]); 0 for an
+    absent id"""
+    sh = [[int(v) for v in plane] for plane in raw["shape"]]
+    o = np.zeros(len(sh[0]), np.float64)
+    for s, n in enumerate(sh[0]):
+        if n:
+            o[s] = _axes(n, sh[1][s], sh[2][s], sh[3][s], sh[4][s], sh[5][s])[2]
+    return o, np.asarray(sh[0], np.int64) > 0
+
+
+def _cell_directions(raw):
+    """``profile_direction`` of every cell slot's own orientation, (0, 0) for an absent id -> int32 [n, 2]"""
+    o, present = _orientations(raw)
+    dirs = profile_direction(o)
+    dirs[~present] = 0
+    return dirs
+
+
+def profile_raw(lab, pix, off, image, channels, bbox, dirs, bins, area=None):
+    """``mseg_cell_profile`` for the whole stack -> (count uint32 [N, n], sums uint64 [C, N, n], extent int64 [2, n]) on the
+    host: per cell slot the pixels and the channel sums of each of the N = ``bins`` bins along ``dirs`` (int32 [n, 2] = uy, ux;
+    ``profile_direction``), and the extreme projections qmin, qmax.  One call per channel run of ``_channel_groups`` and at
+    most MAX_PROFILE_CHANNELS channels per call, one download per call.  ``bbox``: int32 [n, 4], the boxes of
+    ``measure_raw``.  The call has no status word: a cell whose bins do not add up to its area has pixels outside the box
+    given for it, which raises here.  ``area``: the areas ``measure_raw`` reported (raw["shape"][0]); None: they are measured
+    here."""
+    lib = _lib.load()
+    dev = lab.device
+    T, H, W = (int(v) for v in lab.shape)
+    n = int(off[-1])
+    N = check_profile(bins)
+    if N is None:
+        raise ValueError("profile_raw: a number of bins is needed")
+    if image is None or not len(channels):
+        raise ValueError("profiles are taken of an image's channels: none given")
+    dirs = np.ascontiguousarray(dirs, np.int32)
+    if dirs.shape != (n, 2):
+        raise ValueError(f"dirs: int32 [{n}, 2] expected, got {dirs.shape}")
+    runs = [(first + k * step, step, min(MAX_PROFILE_CHANNELS, cnt - k))
+            for first, step, cnt in _channel_groups(list(channels)) for k in range(0, cnt, MAX_PROFILE_CHANNELS)]
+    if n == 0:
+        return np.zeros((N, 0), np.uint32), np.zeros((len(channels), N, 0), np.uint64), np.zeros((2, 0), np.int64)
+    if area is None:
+        area = measure_raw(lab, pix, off)["shape"][0]
+    off_d = _offsets_to_device(off, dev)
+    bbox_d = torch.from_numpy(np.ascontiguousarray(bbox, np.int32).reshape(n, 4)).to(dev)
+    dirs_d = torch.from_numpy(dirs).to(dev)
+    count, extent, sums = None, None, []
+    for run in runs:
+        Cg = run[2]
+        out = torch.empty(Cg * N * n + 2 * n + (N * n + 1) // 2, dtype=torch.int64, device=dev)   # sums, extent, count: one download
+        s_ptr = out.data_ptr()
+        e_ptr = s_ptr + 8 * Cg * N * n
+        _lib.check(lib.mseg_cell_profile(lab.data_ptr(), pix, T, H, W, off_d.data_ptr(), n, *_channel_run(image, run),
+                                         bbox_d.data_ptr(), dirs_d.data_ptr(), N, e_ptr + 16 * n, s_ptr, e_ptr, _stream(dev)),
+                   "cell_profile")
+        host = out.cpu().numpy()
+        sums.append(host[:Cg * N * n].view(np.uint64).reshape(Cg, N, n))
+        extent = host[Cg * N * n:Cg * N * n + 2 * n].reshape(2, n)
+        count = host[Cg * N * n + 2 * n:].view(np.uint32)[:N * n].reshape(N, n)
+        if not np.array_equal(count.sum(axis=0, dtype=np.int64), np.asarray(area).astype(np.int64)):
+            raise RuntimeError("mseg_cell_profile: a cell has pixels outside the bounding box given for it")
+    return count, np.concatenate(sums, axis=0), extent
+
+
+def pole_bins(bins):
+    """the POLE bins of a profile of N = ``bins`` bins, those whose centre lies in the outer quarters of the extent: 4 b + 2 < N
+    (the end of bin 0) and 4 b + 2 > 3 N (the other end) -> (list, list); N = 2 and 3 have none"""
+    N = int(bins)
+    return [b for b in range(N) if 4 * b + 2 < N], [b for b in range(N) if 4 * b + 2 > 3 * N]
+
+
+def profile_columns(count, sums):
+    """(pole_mid_ratio, pole_asym, profile_peak) of one channel from the bin counts and bin sums (integers, sums < 2^53): count
+    [N] and sums [N] of one cell -> three Python floats; count [N, n] and sums [N, n] of n cells -> three lists of n floats.
+    pole_mid_ratio: the mean value of the pixels in the pole bins (``pole_bins``) over the mean of the pixels in the other
+    bins; NaN when either group is empty (or both means are 0; inf over a mean of 0).  pole_asym: |A - B| / (A + B) with A, B
+    the mean values of the pole bins at the two ends; NaN when an end is empty or A + B = 0.  profile_peak: the centre
+    (2 b + 1) / N - 1 of the non-empty bin with the largest mean, ties to the smaller b, the means compared as the exact
+    integers sum_i count_j against sum_j count_i; NaN without a pixel.  The group sums are numpy's (int64, exact), every
+    quotient is one division of Python integers.  The peak starts from numpy's first largest fp64 mean: rounding is
+    monotone, so the bin of the largest exact mean is among the bins that share the largest rounded one, and only cells
+    where several bins share it are compared, in integers."""
+    cnt, sm = np.asarray(count).astype(np.int64), np.asarray(sums).astype(np.int64)
+    if cnt.ndim == 1:
+        return tuple(col[0] for col in profile_columns(cnt[:, None], sm[:, None]))
+    N, n = cnt.shape
+    nan, inf = float("nan"), float("inf")
+    lo, hi = pole_bins(N)
+    ca, sa, cb, sb = cnt[lo].sum(axis=0), sm[lo].sum(axis=0), cnt[hi].sum(axis=0), sm[hi].sum(axis=0)
+    cp, sp = ca + cb, sa + sb
+    cm, smid = cnt.sum(axis=0) - cp, sm.sum(axis=0) - sp
+    ratio = [nan if p == 0 or m == 0 or (u == 0 and v == 0) else ((v * m) / (p * u) if u else inf)
+             for p, m, u, v in zip(cp.tolist(), cm.tolist(), smid.tolist(), sp.tolist())]
+    asym = [abs(x * b - y * a) / (x * b + y * a) if a and b and x * b + y * a else nan
+            for a, b, x, y in zip(ca.tolist(), cb.tolist(), sa.tolist(), sb.tolist())]
+    mean = np.where(cnt > 0, sm / np.maximum(cnt, 1), -1.0)
+    top, best = mean.max(axis=0, initial=-1.0), mean.argmax(axis=0)
+    for s in np.flatnonzero(((mean == top).sum(axis=0) > 1) & (top >= 0)).tolist():
+        k = -1
+        for b in np.flatnonzero(mean[:, s] == top[s]).tolist():
+            if k < 0 or int(sm[b, s]) * int(cnt[k, s]) > int(sm[k, s]) * int(cnt[b, s]):
+                k = b
+        best[s] = k
+    peak = np.where(top >= 0, (2 * best + 1) / N - 1, np.nan)
+    return ratio, asym, peak.tolist()
+
+
+def axis_extent(qmin, qmax):
+    """the pole-to-pole length of a cell's pixel set along its orientation, in pixels: (qmax - qmin) / 16384 + 1"""
+    return (int(qmax) - int(qmin)) / PROFILE_UNIT + 1
+
+
+def profiles_from_raw(off, area, channels, count, sums):
+    """the DataFrame of ``cell_profiles`` from the integers of ``profile_raw``: one row per present cell, channel and bin,
+    ordered by (frame, channel, label, bin); bin_pos = (2 b + 1) / N - 1, mean = sum / count, NaN for an empty bin"""
+    off = np.asarray(off, np.int64)
+    count, sums = np.asarray(count), np.asarray(sums)
+    N, n = count.shape
+    rows = {c: [] for c in PROFILE_TABLE_COLUMNS}
+    pos = [(2 * b + 1) / N - 1 for b in range(N)]
+    cnt = count.astype(np.int64).T.tolist()                       # [n][N]
+    per_channel = [plane.T.tolist() for plane in sums]            # [C][n][N]
+    for t in range(len(off) - 1):
+        for ci, c in enumerate(channels):
+            sm = per_channel[ci]
+            for s in range(int(off[t]), int(off[t + 1])):
+                if int(area[s]) == 0:
+                    continue
+                for b in range(N):
+                    k, v = cnt[s][b], int(sm[s][b])
+                    for name, val in zip(PROFILE_TABLE_COLUMNS, (t, int(c), s - int(off[t]) + 1, b, pos[b], k, v,
+                                                                 v / k if k else float("nan"))):
+                        rows[name].append(val)
+    return pd.DataFrame(rows, columns=PROFILE_TABLE_COLUMNS)
+
+
+def cell_profiles(mask, img, channels=None, bins=16, device=None):
+    """ The intensity profiles of a segmented stack along every cell's axis: one row per cell, channel and bin, ordered by
+    (frame, channel, label, bin).
+
+    Every pixel (y, x) of a cell is projected on the cell's integer direction (uy, ux) = ``profile_direction`` of the table's
+    ``orientation``: q = uy y + ux x; the bins divide the cell's own projected extent qmin .. qmax, from pole to pole of the
+    pixel set, into ``bins`` (2 .. 32) equal parts: bin b = floor((q - qmin) bins / (qmax - qmin + 1)), exact (csrc/profile.hip
+    ``mseg_cell_profile``).  ``count``: the pixels of the bin, ``sum``: the sum of the channel's values over
+    them, ``mean`` = sum / count (NaN for an empty bin), ``bin_pos``: the bin's centre (2 b + 1) / bins - 1 in -1 .. 1.  Bin 0
+    is the end with the smaller projection, the sense in which the spots' axis_pos grows; the sense is arbitrary, because a
+    cell has no head.  ``channels``: indices into the channel axis of ``img`` (default: all).
+    Whole pixels; the profile runs along the straight orientation axis, not along the midline: a strongly bent or
+    filamentous cell is folded onto its chord; the bins divide the projected extent, not arc length; a bin thinner than a
+    pixel row stays empty (count 0, mean NaN); no background subtraction, no normalisation across cells, no demograph
+    image; uint8 / uint16 images only.
+    :return: pandas.DataFrame with the columns PROFILE_TABLE_COLUMNS.
+    """
+    bins = check_profile(bins)
+    if bins is None:
+        raise ValueError("cell_profiles: a number of bins in 2 .. 32 is needed")
+    if img is None:
+        raise ValueError("profiles are taken of an image's channels: no image given")
+    dev = _device(device)
+    with torch.cuda.device(dev):
+        lab, pix = _labels_to_device(mask, dev)
+        T, H, W = (int(v) for v in lab.shape)
+        off = np.zeros(T + 1, np.int64)
+        np.cumsum(_frame_counts(lab), out=off[1:])
+        image = _image_to_device(img, (T, H, W), dev)
+        if image is None:
+            raise ValueError("only uint8 / uint16 images are measured")
+        channels = list(range(image[3])) if channels is None else [int(c) for c in channels]
+        if any(c < 0 or c >= image[3] for c in channels):
+            raise ValueError(f"channels {channels} requested, the image has {image[3]}")
+        if not channels:
+            raise ValueError("profiles are taken of an image's channels: none is measured")
+        raw = measure_raw(lab, pix, off)
+        count, sums, _ = profile_raw(lab, pix, off, image, channels, raw["bbox"], _cell_directions(raw), bins,
+                                     raw["shape"][0])
+    return profiles_from_raw(off, raw["shape"][0], channels, count, sums)
+
+
 def assemble_tracks(frame, label, pred, overlap, min_overlap=1, gap=None):
     """ Track ids from overlap links; pure host code, O(cells).
 
@@ -1090,7 +1310,7 @@ def _neighborhood(v):
 
 
 def table_from_sums(off, H, W, raw, channels=(), links=None, min_overlap=1, shift=None, hull=None, midline=None,
-                    order_stats=None, neighbors=None, spots=None, field=None, tile=None, gaps=None):
+                    order_stats=None, neighbors=None, spots=None, field=None, tile=None, gaps=None, profile=None):
     """the DataFrame from the integer sums of ``measure_raw`` (and ``links`` = (pred, overlap) or None); host arithmetic in
     Python integers and fp64.  ``shift``: int [T, 2], the (dy, dx) of every frame against its predecessor the links were
     taken under (row 0 ignored), or None: with it the drift columns follow the link columns.  ``hull``: int [10, n], the
@@ -1116,7 +1336,9 @@ def table_from_sums(off, H, W, raw, channels=(), links=None, min_overlap=1, shif
     ``shift``), or None: with it flow_y / flow_x follow the drift columns: the field value of the tile that holds the pixel
     (floor(centroid_y), floor(centroid_x)), 0 in frame 0.  ``gaps``: int [n], the pred_gap of ``close_gaps`` (with its pred and
     overlap as ``links``), or None: with it pred_gap follows the link, drift and flow columns and the tracks are assembled
-    over the gaps"""
+    over the gaps.  ``profile``: (count [N, n], sums [C, N, n], extent [2, n]), the integers of ``profile_raw``, or None: with it
+    the table ends with axis_extent = ``axis_extent`` of the cell's extreme projections and, per measured channel,
+    pole_mid_ratio_ch{c}, pole_asym_ch{c} and profile_peak_ch{c} = ``profile_columns`` of the cell's bins"""
     off = np.asarray(off, np.int64)
     area = raw["shape"][0]
     if field is not None and shift is None:
@@ -1126,8 +1348,17 @@ def table_from_sums(off, H, W, raw, channels=(), links=None, min_overlap=1, shif
         raise ValueError("percentiles are taken of an image's channels: none is measured")
     if spots is not None and not len(channels):
         raise ValueError("spots are taken of an image's channels: none is measured")
+    if profile is not None and not len(channels):
+        raise ValueError("profiles are taken of an image's channels: none is measured")
     rows = {c: [] for c in columns(channels, links is not None, shift is not None, hull is not None, midline is not None, pct,
-                                   neighbors is not None, spots is not None, field is not None, gaps is not None)}
+                                   neighbors is not None, spots is not None, field is not None, gaps is not None,
+                                   profile is not None)}
+    if profile is not None:
+        pf_q = np.asarray(profile[2]).astype(np.int64).reshape(2, len(area))
+        pf_len = ((pf_q[1] - pf_q[0]) / PROFILE_UNIT + 1).tolist()                            # ``axis_extent``, all cells at once
+        pf_bins = np.asarray(profile[0]).shape[0]                 # N: a stack without a cell still has its bins
+        pf_cols = [profile_columns(profile[0], plane)                                         # [C][3][n]
+                   for plane in np.asarray(profile[1]).reshape(len(channels), pf_bins, len(area))]
     if field is not None:
         field = np.asarray(field, np.int64).copy()
         field[0] = 0
@@ -1194,6 +1425,10 @@ def table_from_sums(off, H, W, raw, channels=(), links=None, min_overlap=1, shif
                 for ci in range(len(channels)):
                     top, total = sp_acc.get((ci, s), (None, 0))
                     vals += [sp_n[ci][s], top / sp_unit if top is not None else float("nan"), total / sp_unit, sp_bg[t][ci]]
+            if profile is not None:
+                vals += [pf_len[s]]
+                for ci in range(len(channels)):
+                    vals += [col[s] for col in pf_cols[ci]]
             for c, v in zip(rows, vals):
                 rows[c].append(v)
     df = pd.DataFrame(rows, columns=list(rows))
@@ -1206,7 +1441,7 @@ def table_from_sums(off, H, W, raw, channels=(), links=None, min_overlap=1, shif
 
 def measure_cells(mask, img=None, channels=None, link=True, min_overlap=1, device=None, drift=None, hull=False,
                   midline=False, percentiles=None, neighbors=None, spots=None, spot_scale=2, flow=None, flow_tile=64,
-                  gap=None):
+                  gap=None, profile=None):
     """ One row per cell of a segmented stack, ordered by (frame, label).
 
     :param mask: label stack [T, H, W] (or one frame [H, W]): host array or device tensor (int16 holding uint16 bits, or
@@ -1279,8 +1514,21 @@ def measure_cells(mask, img=None, channels=None, link=True, min_overlap=1, devic
         linking of spots over time.  Needs ``img`` and at least one measured channel.
     :param spot_scale: s, a whole number in 1 .. 5 (default 2): the band-pass is the difference of two binomial smoothings
         with sigma = sqrt(s / 2) and sqrt(s) pixels: foci of about that radius answer best.  Read only with ``spots``.
+    :param profile: None (default): off.  N, a whole number of bins in 2 .. 32: the table ends with WHERE ALONG THE CELL
+        the signal of every measured channel sits.  The cell's pixels are projected on its ``orientation`` (as the integer
+        direction ``profile_direction``), the projected extent is cut into N equal bins from pole to pole of the pixel set,
+        and every bin's pixels and channel sums come from the device (``cell_profiles``; csrc/profile.hip).
+        axis_extent: the pole-to-pole length of the pixel set along the orientation, in pixels; pole_mid_ratio_ch{c}: the
+        mean value of the pixels in the pole bins (bin centre in the outer quarters of the extent) over the mean of the
+        others (> 1: polar, < 1: mid-cell; NaN when either group is empty, as for N < 4); pole_asym_ch{c}: |A - B| / (A + B)
+        of the two ends' pole means (0: both poles alike, 1: all at one pole); profile_peak_ch{c}: the centre, in -1 .. 1, of
+        the bin with the largest mean (ties to the lower bin).  Bin 0 is the end with the smaller projection, the sense in
+        which the spots' axis_pos grows; the sense is arbitrary, because a cell has no head: read |profile_peak|.  Whole
+        pixels, along the straight orientation axis: a bent or filamentous cell is folded onto its chord, the bins divide
+        the projected extent, not arc length; no background subtraction, no normalisation across cells.  ``cell_profiles``
+        gives the profiles themselves.  Needs ``img`` and at least one measured channel.
     :return: pandas.DataFrame with the columns of ``columns(channels, link, drift is not None, hull, midline, percentiles,
-        neighbors is not None, spots is not None, flow is not None, gap is not None)``.
+        neighbors is not None, spots is not None, flow is not None, gap is not None, profile is not None)``.
     """
     drift = check_drift(drift)
     flow, flow_tile = check_flow(flow, flow_tile)
@@ -1289,6 +1537,9 @@ def measure_cells(mask, img=None, channels=None, link=True, min_overlap=1, devic
     percentiles = check_percentiles(percentiles)
     neighbors = check_neighbors(neighbors)
     spots = check_spots(spots, spot_scale)
+    profile = check_profile(profile)
+    if profile is not None and img is None:
+        raise ValueError("profiles are taken of an image's channels: no image given")
     if percentiles and img is None:
         raise ValueError("percentiles are taken of an image's channels: no image given")
     if spots is not None and img is None:
@@ -1318,6 +1569,8 @@ def measure_cells(mask, img=None, channels=None, link=True, min_overlap=1, devic
             raise ValueError("percentiles are taken of an image's channels: none is measured")
         if spots is not None and not channels:
             raise ValueError("spots are taken of an image's channels: none is measured")
+        if profile is not None and not channels:
+            raise ValueError("profiles are taken of an image's channels: none is measured")
         raw = measure_raw(lab, pix, off, image, channels)
         shift = pick_drift(drift_raw(lab, pix, off, drift)) if drift is not None else None
         field = pick_flow(flow_raw(lab, pix, off, shift, flow, flow_tile), shift) if flow is not None else None
@@ -1338,8 +1591,10 @@ def measure_cells(mask, img=None, channels=None, link=True, min_overlap=1, devic
             stats = (percentiles,) + order_stats_raw(lab, pix, off, image, channels, raw["bbox"], ranks, bg_ranks)
         near = neighbors_raw(lab, pix, off, neighbors)[0] if neighbors is not None else None
         foci = (spots[1],) + spots_raw(lab, pix, off, image, channels, *spots) if spots is not None else None
+        bins = profile_raw(lab, pix, off, image, channels, raw["bbox"], _cell_directions(raw), profile,
+                           raw["shape"][0]) if profile is not None else None
     return table_from_sums(off, H, W, raw, channels, links, min_overlap, shift, outline, skel, stats, near, foci, field,
-                           flow_tile if field is not None else None, gaps)
+                           flow_tile if field is not None else None, gaps, bins)
 
 
 def write_cells(df, csv_path):

@@ -140,6 +140,11 @@ class InferWorker(QObject):
     # spots; whole pixels, a fixed threshold; inference/cells.py); spot_scale: 1 .. 5, the size of the foci
     spots = None
     spot_scale = 2
+    # [extension] cell_table: None = off; N, a whole number of bins in 2 .. 32: the table ends with where along the cell the
+    # signal of every measured channel sits (pole-to-pole extent, pole / mid-cell ratio, pole asymmetry, brightest bin of the
+    # intensity profile along the cell's orientation; profile_table gives the profiles; whole pixels, the straight axis;
+    # inference/cells.py)
+    profile = None
     # [extension] test-time augmentation (inference/tta.py): 1 = off (no existing route changes), 2 / 4 / 8 =
     # every frame is predicted under that many flips / rotations, the predictions are mapped back and averaged (fp32, in
     # member order) and the average is segmented: K network forwards per frame.  Whole-frame inference only
@@ -884,17 +889,18 @@ class InferWorker(QObject):
         tile-wise displacement field around it (tiles of ``self.flow_tile`` pixels); with ``self.hull`` set, with
         the outline columns; with ``self.midline`` set, with the midline columns; with ``self.percentiles`` set, with the
         percentile columns; with ``self.neighbors`` set, with the neighbourhood columns; with ``self.spots`` set, with the
-        spot columns at ``self.spot_scale``. """
+        spot columns at ``self.spot_scale``; with ``self.profile`` set, with the profile columns of that many bins. """
         from .cells import measure_cells
         df = measure_cells(results, img, link=True, min_overlap=self.min_overlap, device=self.device, drift=self.drift,
                            hull=self.hull, midline=self.midline, percentiles=self.percentiles, neighbors=self.neighbors,
                            spots=self.spots, spot_scale=self.spot_scale, flow=self.flow, flow_tile=self.flow_tile,
-                           gap=self.gap)
+                           gap=self.gap, profile=self.profile)
         if img is not None and channels is not None:      # the view holds the chosen channels only: name them by source
             names = {f'{k}_ch{i}': f'{k}_ch{int(c)}' for i, c in reversed(list(enumerate(channels)))
                      for k in ('mean', 'std', 'min', 'max', 'sum', 'bg_mean') +
                      tuple(f'{b}p{int(q)}' for q in (self.percentiles or ()) for b in ('', 'bg_')) +
-                     (('n_spots', 'spot_max', 'spot_sum', 'bg_spots') if self.spots is not None else ())}
+                     (('n_spots', 'spot_max', 'spot_sum', 'bg_spots') if self.spots is not None else ()) +
+                     (('pole_mid_ratio', 'pole_asym', 'profile_peak') if self.profile is not None else ())}
             df = df.rename(columns=names)
         return df
 
@@ -905,6 +911,17 @@ class InferWorker(QObject):
         go into the ``channel`` column).  Whole pixels, a fixed threshold; spots on the background are left out. """
         from .cells import cell_spots
         df = cell_spots(results, img, spots=self.spots, spot_scale=self.spot_scale, device=self.device)
+        if channels is not None:
+            df['channel'] = df['channel'].map(lambda i: int(channels[i]))
+        return df
+
+    def profile_table(self, results, img, channels=None):
+        """ [extension] The intensity profiles of a segmented stack along every cell's axis (inference/cells.py
+        ``cell_profiles``): one row per cell, channel and bin of ``self.profile`` bins.  ``img`` as for ``cell_table``;
+        ``channels``: the numbers of the source image the view's channels have (they go into the ``channel`` column).  Whole
+        pixels, along the straight orientation axis; no background subtraction. """
+        from .cells import cell_profiles
+        df = cell_profiles(results, img, bins=self.profile, device=self.device)
         if channels is not None:
             df['channel'] = df['channel'].map(lambda i: int(channels[i]))
         return df
