@@ -46,6 +46,7 @@ orientation axis (a bent cell is folded onto its chord), no background subtracti
 """
 import ctypes as C
 import math
+import types
 
 import numpy as np
 import pandas as pd
@@ -103,16 +104,25 @@ def columns(channels=(), link=True, drift=False, hull=False, midline=False, perc
         raise ValueError("the flow columns follow the drift columns: flow needs drift")
     if gap and not link:
         raise ValueError("pred_gap belongs to the link columns: gap needs link")
-    cols = list(SHAPE_COLUMNS)
-    for c in channels:
-        cols += [name.format(c=int(c)) for name in CHANNEL_COLUMNS]
-    return cols + (list(LINK_COLUMNS) if link else []) + (list(DRIFT_COLUMNS) if drift else []) + \
-        (list(FLOW_COLUMNS) if flow else []) + (list(GAP_COLUMNS) if gap else []) + \
-        (list(HULL_COLUMNS) if hull else []) + (list(MIDLINE_COLUMNS) if midline else []) + \
-        [name.format(p=int(q), c=int(c)) for name in (PERCENTILE_COLUMNS if percentiles else ()) for c in channels
-         for q in percentiles] + (list(NEIGHBOR_COLUMNS) if neighbors else []) + \
-        [name.format(c=int(c)) for c in (channels if spots else ()) for name in SPOT_COLUMNS] + \
-        ((['axis_extent'] + [name.format(c=int(c)) for c in channels for name in PROFILE_COLUMNS]) if profile else [])
+    on = dict(link=link, drift=drift, flow=flow, gap=gap, hull=hull, midline=midline, percentiles=bool(percentiles),
+              neighbors=neighbors, spots=spots, profile=profile)
+    return [name for key, names, _ in _FAMILIES if on.get(key, True) for name in names(channels, percentiles)]
+
+
+def channel_stems(percentiles=(), spots=False, profile=False):
+    """the stems k of the table's per-channel columns k_ch{c}, for a caller that numbers the channels its own way
+    (``InferWorker.cell_table``)"""
+    names = CHANNEL_COLUMNS + [name.replace('{p}', str(int(q))) for q in percentiles for name in PERCENTILE_COLUMNS] + \
+        (SPOT_COLUMNS if spots else []) + (PROFILE_COLUMNS if profile else [])
+    return [name[:-len('_ch{c}')] for name in names]
+
+
+def _need_channels(have, why, **families):
+    """the refusal of the families that read an image (percentiles=, spots=, profiles= ..: on or off, in the order in which
+    they refuse) where ``have``, the image or the channels to read, is missing"""
+    for what, on in families.items():
+        if on and not have:
+            raise ValueError(f"{what.replace('_', ' ')} are taken of an image's channels: {why}")
 
 
 def _device(device=None):
@@ -234,15 +244,50 @@ def _channel_run(image, group):
     return base + first * cs0 * (1 if ipix == _lib.PIX_U8 else 2), ipix, count, fs, step * cs0, rs, ps
 
 
+class _Stack:
+    """What the entry points make of their arguments before the first device call: ``dev``; the labels on it, ``lab`` and
+    ``pix`` (``_labels_to_device``), with ``T``, ``H``, ``W``; ``off``, the host table int64 [T + 1] of label offsets
+    (``_frame_counts``); with an image, ``image``, the tuple of ``_image_to_device`` (uint8 / uint16 only), and ``channels``,
+    the indices to measure as a list (default: all; each must exist); without one, None and []."""
+
+    def __init__(self, mask, img=None, channels=None, device=None):
+        self.dev = _device(device)
+        with torch.cuda.device(self.dev):
+            self.lab, self.pix = _labels_to_device(mask, self.dev)
+            self.T, self.H, self.W = (int(v) for v in self.lab.shape)
+            self.off = np.zeros(self.T + 1, np.int64)
+            np.cumsum(_frame_counts(self.lab), out=self.off[1:])
+            self.image, self.channels = None, []
+            if img is not None:
+                self.image = _image_to_device(img, (self.T, self.H, self.W), self.dev)
+                if self.image is None:
+                    raise ValueError("only uint8 / uint16 images are measured")
+                self.channels = list(range(self.image[3])) if channels is None else [int(c) for c in channels]
+                if any(c < 0 or c >= self.image[3] for c in self.channels):
+                    raise ValueError(f"channels {self.channels} requested, the image has {self.image[3]}")
+
+
+def _raw_args(lab, off, off_d=None):
+    """what every ``*_raw`` opens with -> (lib, dev, T, H, W, n, off_d): the library, the device and the sizes of the labels,
+    the number of label slots, and ``off`` on the device: uploaded here, once per call, unless the caller has it there"""
+    T, H, W = (int(v) for v in lab.shape)
+    return _lib.load(), lab.device, T, H, W, int(off[-1]), _offsets_to_device(off, lab.device) if off_d is None else off_d
+
+
+def _with_status(items, dtype, dev, launch):
+    """``items`` zeroed elements and the call's status word behind them in ONE device tensor, so that one download brings
+    both: ``launch(address of the items, address of the status word)`` -> (the items on the host, the status word)"""
+    out = torch.zeros(items + 1, dtype=dtype, device=dev)
+    launch(out.data_ptr(), out.data_ptr() + items * out.element_size())
+    host = out.cpu().numpy()
+    return host[:-1], int(host[-1:].view(np.int32)[0])
+
+
 def measure_raw(lab, pix, off, image=None, channels=()):
     """The integer sums of ``mseg_cell_measure`` as host arrays.  lab: device labels [T, H, W]; off: int64 [T + 1] host
     table; image: the tuple of ``_image_to_device``.  -> dict: shape uint64 [6, n], bbox int32 [n, 4], ch_sums uint64
     [2, C, n], ch_minmax uint32 [2, C, n], bg_sums uint64 [3, T, C], bg_minmax uint32 [2, T, C]"""
-    lib = _lib.load()
-    dev = lab.device
-    T, H, W = (int(v) for v in lab.shape)
-    n = int(off[-1])
-    off_d = _offsets_to_device(off, dev)
+    lib, dev, T, H, W, n, off_d = _raw_args(lab, off)
     shape = torch.zeros((6, max(n, 1)), dtype=torch.int64, device=dev)
     bbox = torch.zeros((max(n, 1), 4), dtype=torch.int32, device=dev)
     out = {"ch_sums": [], "ch_minmax": [], "bg_sums": [], "bg_minmax": []}
@@ -274,9 +319,6 @@ def hull_raw(lab, pix, off, bbox):
     """``mseg_cell_hull`` for the whole stack -> int64 [10, n] on the host: perimeter, hull_n, hull_area2, feret2, ay, ax, by,
     bx, minw_num, minw_den2 per cell slot, zeros for absent ids.  ``bbox``: int32 [n, 4], the boxes of ``measure_raw``; a
     cell with a pixel outside its box makes the device set its status word, which raises here."""
-    lib = _lib.load()
-    dev = lab.device
-    T, H, W = (int(v) for v in lab.shape)
     n = int(off[-1])
     bbox = np.ascontiguousarray(bbox, np.int32).reshape(n, 4)
     row_off = np.zeros(n + 1, np.int64)        # corner rows of a present cell: r1 - r0 + 1; an absent one (r1 == 0) has none
@@ -284,27 +326,22 @@ def hull_raw(lab, pix, off, bbox):
     n_rows = int(row_off[-1])
     if n == 0:
         return np.zeros((10, 0), np.int64)
-    off_d = _offsets_to_device(off, dev)
+    lib, dev, T, H, W, n, off_d = _raw_args(lab, off)
     bbox_d, row_d = torch.from_numpy(bbox).to(dev), torch.from_numpy(row_off).to(dev)
-    out = torch.zeros(10 * n + 1, dtype=torch.int64, device=dev)      # the last element holds the status word: one download
     ws = _workspace(lib.mseg_cell_hull_workspace_bytes(n, n_rows), dev,
                     f"mseg_cell_hull: no workspace for {n} cells with {n_rows} rows")
-    _lib.check(lib.mseg_cell_hull(lab.data_ptr(), pix, T, H, W, off_d.data_ptr(), n, bbox_d.data_ptr(), row_d.data_ptr(),
-                                  n_rows, out.data_ptr(), out.data_ptr() + 80 * n, ws.data_ptr(), ws.numel(), _stream(dev)),
-               "cell_hull")
-    host = out.cpu().numpy()
-    if host[-1:].view(np.int32)[0] != 0:
+    ints, status = _with_status(10 * n, torch.int64, dev, lambda out, word: _lib.check(lib.mseg_cell_hull(
+        lab.data_ptr(), pix, T, H, W, off_d.data_ptr(), n, bbox_d.data_ptr(), row_d.data_ptr(), n_rows, out, word,
+        ws.data_ptr(), ws.numel(), _stream(dev)), "cell_hull"))
+    if status:
         raise RuntimeError("mseg_cell_hull: a cell has pixels outside the bounding box given for it")
-    return host[:-1].reshape(10, n)
+    return ints.reshape(10, n)
 
 
 def midline_raw(lab, pix, off, bbox, skeleton=False):
     """``mseg_cell_midline`` for the whole stack -> int64 [12, n] on the host: skel_n, n_orth, n_diag, n_end, n_branch, rounds,
     e0_y, e0_x, e0_d2, e1_y, e1_x, e1_d2 per cell slot, zeros for absent ids; with ``skeleton`` also the uint8 [T, H, W] image
     of all skeletons.  ``bbox``: int32 [n, 4], the boxes of ``measure_raw``.  A set status word raises."""
-    lib = _lib.load()
-    dev = lab.device
-    T, H, W = (int(v) for v in lab.shape)
     n = int(off[-1])
     bbox = np.ascontiguousarray(bbox, np.int32).reshape(n, 4)
     b = bbox.astype(np.int64)
@@ -313,24 +350,34 @@ def midline_raw(lab, pix, off, bbox, skeleton=False):
     n_words = int(word_off[-1])
     if n == 0:
         ints = np.zeros((12, 0), np.int64)
-        return (ints, np.zeros((T, H, W), np.uint8)) if skeleton else ints
+        return (ints, np.zeros(tuple(lab.shape), np.uint8)) if skeleton else ints
+    lib, dev, T, H, W, n, off_d = _raw_args(lab, off)
     skel = torch.empty((T, H, W), dtype=torch.uint8, device=dev) if skeleton else None
-    off_d = _offsets_to_device(off, dev)
     bbox_d, word_d = torch.from_numpy(bbox).to(dev), torch.from_numpy(word_off).to(dev)
-    out = torch.zeros(12 * n + 1, dtype=torch.int64, device=dev)      # the last element holds the status word: one download
     ws = _workspace(lib.mseg_cell_midline_workspace_bytes(n, n_words), dev,
                     f"mseg_cell_midline: no workspace for {n} cells with {n_words} words")
-    _lib.check(lib.mseg_cell_midline(lab.data_ptr(), pix, T, H, W, off_d.data_ptr(), n, bbox_d.data_ptr(), word_d.data_ptr(),
-                                     n_words, out.data_ptr(), skel.data_ptr() if skeleton else None, out.data_ptr() + 96 * n,
-                                     ws.data_ptr(), ws.numel(), _stream(dev)), "cell_midline")
-    host = out.cpu().numpy()
-    status = int(host[-1:].view(np.int32)[0])
+    ints, status = _with_status(12 * n, torch.int64, dev, lambda out, word: _lib.check(lib.mseg_cell_midline(
+        lab.data_ptr(), pix, T, H, W, off_d.data_ptr(), n, bbox_d.data_ptr(), word_d.data_ptr(), n_words, out,
+        skel.data_ptr() if skeleton else None, word, ws.data_ptr(), ws.numel(), _stream(dev)), "cell_midline"))
     if status & 1:
         raise RuntimeError("mseg_cell_midline: a cell has pixels outside the bounding box given for it")
     if status:
         raise RuntimeError("mseg_cell_midline: a cell was still being thinned at the round cap")
-    ints = host[:-1].reshape(12, n)
+    ints = ints.reshape(12, n)
     return (ints, skel.cpu().numpy()) if skeleton else ints
+
+
+def _whole(v, lo, hi, what, floats=True):
+    """the one rule under the ``check_*`` functions: ``v`` as an int if it is a whole number in lo .. hi, else ValueError "``what``
+    expected, got v".  Never a bool, a str or bytes; else what equals its ``int`` (3.0, a numpy integer; what ``int`` refuses does
+    not), without ``floats`` integers only"""
+    try:
+        if not isinstance(v, (bool, str, bytes)) and (floats or isinstance(v, (int, np.integer))) and int(v) == v and \
+                lo <= int(v) <= hi:
+            return int(v)
+    except (TypeError, ValueError, OverflowError):
+        pass
+    raise ValueError(f"{what} expected, got {v!r}")
 
 
 def check_percentiles(p):
@@ -344,13 +391,7 @@ def check_percentiles(p):
         raise ValueError(f"percentiles: None or a sequence of whole numbers in 0 .. 100 expected, got {p!r}") from None
     out = []
     for v in vals:
-        try:
-            ok = not isinstance(v, (bool, str, bytes)) and int(v) == v and 0 <= int(v) <= 100
-        except (TypeError, ValueError, OverflowError):
-            ok = False
-        if not ok:
-            raise ValueError(f"percentiles: whole numbers in 0 .. 100 expected, got {v!r}")
-        out.append(int(v))
+        out.append(_whole(v, 0, 100, "percentiles: whole numbers in 0 .. 100"))
     if len(out) > MAX_PERCENTILES or len(set(out)) != len(out):
         raise ValueError(f"percentiles: at most {MAX_PERCENTILES} distinct values expected, got {out}")
     return tuple(out)
@@ -386,18 +427,13 @@ def order_stats_raw(lab, pix, off, image, channels, bbox, ranks, bg_ranks):
     [R, T, C]) on the host: per cell slot (frame) and channel the pixel value of rank ranks[j, s] (bg_ranks[j, t]) in ascending
     order.  ``bbox``: int32 [n, 4], the boxes of ``measure_raw``; ranks int64 [R, n], bg_ranks int64 [R, T].  A rank beyond a
     cell's pixels inside its box (or beyond a frame's background) makes the device set its status word, which raises here."""
-    lib = _lib.load()
-    dev = lab.device
-    T, H, W = (int(v) for v in lab.shape)
-    n = int(off[-1])
+    lib, dev, T, H, W, n, off_d = _raw_args(lab, off)
     ranks = np.ascontiguousarray(ranks, np.int64)
     bg_ranks = np.ascontiguousarray(bg_ranks, np.int64)
     R = int(bg_ranks.shape[0])
-    if image is None or not len(channels):
-        raise ValueError("order statistics are taken of an image's channels: none given")
+    _need_channels(image is not None and len(channels), "none given", order_statistics=True)
     if bg_ranks.shape != (R, T) or ranks.shape != (R, n):
         raise ValueError(f"ranks [{R}, {n}] and bg_ranks [{R}, {T}] expected, got {ranks.shape} and {bg_ranks.shape}")
-    off_d = _offsets_to_device(off, dev)
     bbox_d = torch.from_numpy(np.ascontiguousarray(bbox, np.int32).reshape(n, 4)).to(dev) if n else None
     ranks_d = torch.from_numpy(ranks).to(dev) if n else None
     bg_ranks_d = torch.from_numpy(bg_ranks).to(dev)
@@ -406,18 +442,17 @@ def order_stats_raw(lab, pix, off, image, channels, bbox, ranks, bg_ranks):
         Cg = group[2]
         ws = _workspace(lib.mseg_cell_order_stats_workspace_bytes(T, n, Cg, R), dev,
                         f"mseg_cell_order_stats: no workspace for T = {T}, {Cg} channels, {R} ranks")
-        out = torch.zeros(R * Cg * n + R * T * Cg + 1, dtype=torch.int32, device=dev)      # values, bg_values, status: one download
-        v_ptr, b_ptr = out.data_ptr(), out.data_ptr() + 4 * R * Cg * n
-        _lib.check(lib.mseg_cell_order_stats(lab.data_ptr(), pix, T, H, W, off_d.data_ptr(), n, *_channel_run(image, group),
-                                             bbox_d.data_ptr() if n else None, R, ranks_d.data_ptr() if n else None,
-                                             bg_ranks_d.data_ptr(), v_ptr if n else None, b_ptr, b_ptr + 4 * R * T * Cg,
-                                             ws.data_ptr(), ws.numel(), _stream(dev)), "cell_order_stats")
-        host = out.cpu().numpy().view(np.uint32)
-        if host[-1] != 0:
+        host, status = _with_status(R * Cg * n + R * T * Cg, torch.int32, dev, lambda out, word: _lib.check(     # values, bg_values
+            lib.mseg_cell_order_stats(lab.data_ptr(), pix, T, H, W, off_d.data_ptr(), n, *_channel_run(image, group),
+                                      bbox_d.data_ptr() if n else None, R, ranks_d.data_ptr() if n else None,
+                                      bg_ranks_d.data_ptr(), out if n else None, out + 4 * R * Cg * n, word, ws.data_ptr(),
+                                      ws.numel(), _stream(dev)), "cell_order_stats"))
+        if status:
             raise RuntimeError("mseg_cell_order_stats: a rank lies beyond the pixels of a cell inside the bounding box given "
                                "for it (or beyond a frame's background)")
+        host = host.view(np.uint32)
         vals.append(host[:R * Cg * n].reshape(R, Cg, n))
-        bgs.append(host[R * Cg * n:-1].reshape(R, T, Cg))
+        bgs.append(host[R * Cg * n:].reshape(R, T, Cg))
     return np.concatenate(vals, axis=1), np.concatenate(bgs, axis=2)
 
 
@@ -427,22 +462,15 @@ def _pow2(v):
 
 def check_drift(drift):
     """the rule of ``measure_cells(drift=...)``, ``InferWorker.drift`` and --drift: None, or an int in 0 .. MAX_DRIFT"""
-    if drift is None:
-        return None
-    if isinstance(drift, bool) or int(drift) != drift or not 0 <= int(drift) <= MAX_DRIFT:
-        raise ValueError(f"drift: None or a whole number of pixels in 0 .. {MAX_DRIFT} expected, got {drift!r}")
-    return int(drift)
+    return None if drift is None else _whole(drift, 0, MAX_DRIFT, f"drift: None or a whole number of pixels in 0 .. {MAX_DRIFT}")
 
 
 def drift_raw(lab, pix, off, max_drift):
     """``mseg_stack_drift`` for the whole stack -> scores uint32 [T - 1, 2R + 1, 2R + 1] on the host: scores[t - 1, dy + R,
     dx + R] = pixels where the foreground of frame t - 1 moved by (dy, dx) lies on the foreground of frame t"""
-    lib = _lib.load()
-    dev = lab.device
-    T, H, W = (int(v) for v in lab.shape)
+    lib, dev, T, H, W, _, off_d = _raw_args(lab, off)
     R = int(max_drift)
     side = 2 * R + 1
-    off_d = _offsets_to_device(off, dev)
     scores = torch.zeros((max(T - 1, 1), side, side), dtype=torch.int32, device=dev)
     ws = _workspace(lib.mseg_stack_drift_workspace_bytes(T, H, W), dev,
                     f"mseg_stack_drift: no workspace for a {T} x {H} x {W} stack")
@@ -475,28 +503,23 @@ def pick_drift(scores):
 def check_flow(flow, tile=64):
     """the rule of ``measure_cells(flow=..., flow_tile=...)``, ``InferWorker.flow`` / ``flow_tile`` and --flow / --flow_tile:
     None, or an int in 0 .. MAX_FLOW, and a tile of FLOW_TILES -> (flow, tile)"""
-    if isinstance(tile, bool) or int(tile) != tile or int(tile) not in FLOW_TILES:
-        raise ValueError(f"flow_tile: one of {', '.join(str(b) for b in FLOW_TILES)} pixels expected, got {tile!r}")
-    if flow is None:
-        return None, int(tile)
-    if isinstance(flow, bool) or int(flow) != flow or not 0 <= int(flow) <= MAX_FLOW:
-        raise ValueError(f"flow: None or a whole number of pixels in 0 .. {MAX_FLOW} expected, got {flow!r}")
-    return int(flow), int(tile)
+    what = f"flow_tile: one of {', '.join(str(b) for b in FLOW_TILES)} pixels"
+    if _whole(tile, min(FLOW_TILES), max(FLOW_TILES), what) not in FLOW_TILES:
+        raise ValueError(f"{what} expected, got {tile!r}")
+    return None if flow is None else _whole(flow, 0, MAX_FLOW, f"flow: None or a whole number of pixels in 0 .. {MAX_FLOW}"), \
+        int(tile)
 
 
 def flow_raw(lab, pix, off, base, radius, tile):
     """``mseg_stack_flow`` for the whole stack -> scores uint32 [T - 1, ty, tx, 2r + 1, 2r + 1] on the host: scores[t - 1, j,
     i, ey + r, ex + r] = pixels of tile (j, i) of frame t where the foreground of frame t - 1 moved by base[t] + (ey, ex)
     lies on the foreground of frame t.  ``base``: int32 [T, 2], row 0 unused"""
-    lib = _lib.load()
-    dev = lab.device
-    T, H, W = (int(v) for v in lab.shape)
+    lib, dev, T, H, W, _, off_d = _raw_args(lab, off)
     r, B = int(radius), int(tile)
     base = np.ascontiguousarray(base, np.int32)
     if base.shape != (T, 2):
         raise ValueError(f"base: int32 [{T}, 2] expected, got {base.shape}")
     ty, tx, side = -(-H // B), -(-W // B), 2 * r + 1
-    off_d = _offsets_to_device(off, dev)
     base_d = torch.from_numpy(base).to(dev)
     scores = torch.zeros((max(T - 1, 1), ty, tx, side, side), dtype=torch.int32, device=dev)
     ws = _workspace(lib.mseg_stack_flow_workspace_bytes(T, H, W), dev,
@@ -532,32 +555,74 @@ def pick_flow(scores, base):
     return field
 
 
-def _links_call(lab, pix, off, cap, shift=None, tile=None):
-    lib = _lib.load()
-    dev = lab.device
+def _motion(lab, shift, field, tile):
+    """the motion argument of ``link_raw`` / ``link_gap_raw``, checked against the stack -> int32 [T, 2] (``shift``), int32
+    [T, ty, tx, 2] (``field``, which goes with ``tile``), or None: same (y, x)"""
     T, H, W = (int(v) for v in lab.shape)
-    n = int(off[-1])
-    off_d = _offsets_to_device(off, dev)
+    if (field is None) != (tile is None) or (field is not None and shift is not None):
+        raise ValueError("field and tile go together, and not with shift")
+    if field is not None:
+        moved = np.ascontiguousarray(field, np.int32)
+        if int(tile) not in FLOW_TILES or moved.shape != (T, -(-H // int(tile)), -(-W // int(tile)), 2):
+            raise ValueError(f"field: int32 [{T}, ceil({H} / tile), ceil({W} / tile), 2] with a tile of {FLOW_TILES} expected, "
+                             f"got {moved.shape} with tile {tile}")
+        return moved
+    if shift is None:
+        return None
+    moved = np.ascontiguousarray(shift, np.int32)
+    if moved.shape != (T, 2):
+        raise ValueError(f"shift: int32 [{T}, 2] expected, got {moved.shape}")
+    return moved
+
+
+def _links_call(lab, pix, off, cap, moved=None, tile=None, back=1, flags=None, off_d=None):
+    """one launch of the links entry point the arguments ask for: ``mseg_cell_links``; with ``moved``: ``_shifted``; with ``tile``
+    as well: ``_field``; with ``flags`` = (want, open): ``_gap``, ``back`` frames back -> (pred [n], overlap [n], status [T])"""
+    lib, dev, T, H, W, n, off_d = _raw_args(lab, off, off_d)
     pred = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
     ovl = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
     status = torch.zeros(T, dtype=torch.int32, device=dev)
+    moved_d = torch.from_numpy(np.ascontiguousarray(moved, np.int32)).to(dev) if moved is not None else None
+    name, motion = "cell_links", ((moved_d.data_ptr(),) if moved is not None else ())
+    if flags is not None:
+        # want, then open, in one upload; the byte after them keeps the tensor (and both addresses) valid for a stack without cells
+        flags_d = torch.from_numpy(np.concatenate([*flags, [False]]).astype(np.uint8)).to(dev)
+        name, motion = "cell_links_gap", (int(back), int(tile) if tile is not None else 0, *(motion or (None,)),
+                                          flags_d.data_ptr(), flags_d.data_ptr() + n)
     ws = _workspace(lib.mseg_cell_links_workspace_bytes(T, n, cap), dev,
-                    f"mseg_cell_links: no workspace for T = {T}, {n} cells, table {cap}")
-    if tile is not None:
-        field_d = torch.from_numpy(np.ascontiguousarray(shift, np.int32)).to(dev)
-        _lib.check(lib.mseg_cell_links_field(lab.data_ptr(), pix, T, H, W, off_d.data_ptr(), n, cap, int(tile),
-                                             field_d.data_ptr(), pred.data_ptr(), ovl.data_ptr(), status.data_ptr(),
-                                             ws.data_ptr(), ws.numel(), _stream(dev)), "cell_links_field")
-    elif shift is None:
-        _lib.check(lib.mseg_cell_links(lab.data_ptr(), pix, T, H, W, off_d.data_ptr(), n, cap, pred.data_ptr(),
-                                       ovl.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)),
-                   "cell_links")
-    else:
-        shift_d = torch.from_numpy(np.ascontiguousarray(shift, np.int32)).to(dev)
-        _lib.check(lib.mseg_cell_links_shifted(lab.data_ptr(), pix, T, H, W, off_d.data_ptr(), n, cap, shift_d.data_ptr(),
-                                               pred.data_ptr(), ovl.data_ptr(), status.data_ptr(), ws.data_ptr(),
-                                               ws.numel(), _stream(dev)), "cell_links_shifted")
+                    f"mseg_{name}: no workspace for T = {T}, {n} cells, table {cap}")
+    if flags is None and moved is not None:
+        name, motion = ("cell_links_field", (int(tile),) + motion) if tile is not None else ("cell_links_shifted", motion)
+    _lib.check(getattr(lib, "mseg_" + name)(lab.data_ptr(), pix, T, H, W, off_d.data_ptr(), n, cap, *motion, pred.data_ptr(),
+                                            ovl.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)), name)
     return pred.cpu().numpy()[:n], ovl.cpu().numpy()[:n], status.cpu().numpy()
+
+
+def _links(lab, pix, off, table_cap, moved, tile, back=1, flags=None, off_d=None):
+    """The body of ``link_raw`` and ``link_gap_raw``: frame t against frame t - ``back`` (``flags`` = (want, open): flagged cells
+    only) in one ``_links_call``, and the redo, alone on the frames t - back .. t, of every frame whose table filled up"""
+    T, H, W = (int(v) for v in lab.shape)
+    if table_cap is None:
+        new = old = np.diff(off)
+        if flags is not None:
+            frame = np.repeat(np.arange(T), new)
+            new, old = (np.bincount(frame[f], minlength=T) for f in flags)
+        pair = int((new[back:] + old[:T - back]).max()) if T > back else 0
+        table_cap = min(max(MIN_TABLE, _pow2(4 * pair)), _pow2(H * W + 1))
+    pred, ovl, status = _links_call(lab, pix, off, int(table_cap), moved, tile, back, flags, off_d)
+    pred, ovl = pred.copy(), ovl.copy()
+    for t in np.nonzero(status)[0]:
+        lo, hi = int(off[t - back]), int(off[t + 1])
+        sub = off[t - back:t + 2] - lo
+        p2, o2, s2 = _links_call(lab[t - back:t + 1], pix, sub, max(MIN_TABLE, _pow2(H * W + 1)),
+                                 None if moved is None else moved[t - back:t + 1], tile, back,
+                                 None if flags is None else tuple(f[lo:hi] for f in flags))
+        if s2.any():
+            raise RuntimeError(f"mseg_cell_links{'' if flags is None else '_gap'}: a table of more than H * W entries "
+                               "reported full")
+        pred[off[t]:off[t + 1]] = p2[sub[back]:]
+        ovl[off[t]:off[t + 1]] = o2[sub[back]:]
+    return pred, ovl
 
 
 def link_raw(lab, pix, off, table_cap=None, shift=None, field=None, tile=None):
@@ -567,43 +632,13 @@ def link_raw(lab, pix, off, table_cap=None, shift=None, field=None, tile=None):
     [T, 2] = (dy, dx) per frame against its predecessor (row 0 unused): the links are taken under these shifts
     (``mseg_cell_links_shifted``); None: same (y, x), as ever.  ``field`` with ``tile``: int32 [T, ty, tx, 2], one (dy, dx)
     per ``tile`` x ``tile`` pixels of every frame (frame 0 unused): the links are taken under it (``mseg_cell_links_field``)."""
-    T, H, W = (int(v) for v in lab.shape)
-    if (field is None) != (tile is None) or (field is not None and shift is not None):
-        raise ValueError("field and tile go together, and not with shift")
-    moved = None                      # the shifts or the field: per frame, entry 0 unused
-    if field is not None:
-        moved = np.ascontiguousarray(field, np.int32)
-        if int(tile) not in FLOW_TILES or moved.shape != (T, -(-H // int(tile)), -(-W // int(tile)), 2):
-            raise ValueError(f"field: int32 [{T}, ceil({H} / tile), ceil({W} / tile), 2] with a tile of {FLOW_TILES} expected, "
-                             f"got {moved.shape} with tile {tile}")
-    elif shift is not None:
-        moved = np.ascontiguousarray(shift, np.int32)
-        if moved.shape != (T, 2):
-            raise ValueError(f"shift: int32 [{T}, 2] expected, got {moved.shape}")
-    k = np.diff(off)
-    if table_cap is None:
-        pair = int((k[1:] + k[:-1]).max()) if T > 1 else 0
-        table_cap = min(max(MIN_TABLE, _pow2(4 * pair)), _pow2(H * W + 1))
-    pred, ovl, status = _links_call(lab, pix, off, int(table_cap), moved, tile)
-    pred, ovl = pred.copy(), ovl.copy()
-    for t in np.nonzero(status)[0]:
-        sub = np.asarray(off[t - 1:t + 2], np.int64) - off[t - 1]
-        p2, o2, s2 = _links_call(lab[t - 1:t + 1], pix, sub, max(MIN_TABLE, _pow2(H * W + 1)),
-                                 None if moved is None else np.stack([np.zeros_like(moved[t]), moved[t]]), tile)
-        if s2.any():
-            raise RuntimeError("mseg_cell_links: a table of more than H * W entries reported full")
-        pred[off[t]:off[t + 1]] = p2[sub[1]:]
-        ovl[off[t]:off[t + 1]] = o2[sub[1]:]
-    return pred, ovl
+    return _links(lab, pix, np.asarray(off, np.int64), table_cap, _motion(lab, shift, field, tile), tile)
 
 
 def check_gap(gap):
     """the rule of ``measure_cells(gap=...)``, ``InferWorker.gap`` and --gap: None, or an int in 1 .. MAX_GAP"""
-    if gap is None:
-        return None
-    if isinstance(gap, bool) or not isinstance(gap, (int, np.integer)) or not 1 <= int(gap) <= MAX_GAP:
-        raise ValueError(f"gap: None or a whole number of missed frames in 1 .. {MAX_GAP} expected, got {gap!r}")
-    return int(gap)
+    return None if gap is None else _whole(gap, 1, MAX_GAP, f"gap: None or a whole number of missed frames in 1 .. {MAX_GAP}",
+                                           floats=False)
 
 
 def compose_motion(moved, g):
@@ -621,29 +656,6 @@ def compose_motion(moved, g):
     return out
 
 
-def _links_gap_call(lab, pix, off, cap, g, want, open_, moved=None, tile=None, off_d=None):
-    lib = _lib.load()
-    dev = lab.device
-    T, H, W = (int(v) for v in lab.shape)
-    n = int(off[-1])
-    if off_d is None:
-        off_d = _offsets_to_device(off, dev)
-    # want, then open, in one upload; the byte after them keeps the tensor (and both addresses) valid for a stack without cells
-    flags = torch.from_numpy(np.concatenate([want, open_, [False]]).astype(np.uint8)).to(dev)
-    pred = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
-    ovl = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
-    status = torch.zeros(T, dtype=torch.int32, device=dev)
-    ws = _workspace(lib.mseg_cell_links_workspace_bytes(T, n, cap), dev,
-                    f"mseg_cell_links_gap: no workspace for T = {T}, {n} cells, table {cap}")
-    moved_d = torch.from_numpy(np.ascontiguousarray(moved, np.int32)).to(dev) if moved is not None else None
-    _lib.check(lib.mseg_cell_links_gap(lab.data_ptr(), pix, T, H, W, off_d.data_ptr(), n, cap, int(g),
-                                       int(tile) if tile is not None else 0,
-                                       moved_d.data_ptr() if moved_d is not None else None, flags.data_ptr(),
-                                       flags.data_ptr() + n, pred.data_ptr(), ovl.data_ptr(), status.data_ptr(),
-                                       ws.data_ptr(), ws.numel(), _stream(dev)), "cell_links_gap")
-    return pred.cpu().numpy()[:n], ovl.cpu().numpy()[:n], status.cpu().numpy()
-
-
 def link_gap_raw(lab, pix, off, g, want, open, shift=None, field=None, tile=None, table_cap=None, off_d=None):
     """``mseg_cell_links_gap`` for the whole stack -> (pred int32 [n], overlap int32 [n]) on the host: per cell of frame t
     flagged in ``want`` the cell of frame t - g flagged in ``open`` that shares the most pixels with it (ties to the smaller
@@ -653,44 +665,16 @@ def link_gap_raw(lab, pix, off, g, want, open, shift=None, field=None, tile=None
     device status word says so) is redone alone, on the g + 1 frames t - g .. t, with a table of more than H * W entries,
     which cannot fill up: the result is always exact.  ``off_d``: ``off`` on the device already (``close_gaps`` uploads it once
     for all its passes), or None."""
-    T, H, W = (int(v) for v in lab.shape)
     g = int(g)
     off = np.asarray(off, np.int64)
     n = int(off[-1])
-    if (field is None) != (tile is None) or (field is not None and shift is not None):
-        raise ValueError("field and tile go together, and not with shift")
+    moved = _motion(lab, shift, field, tile)
     if not 1 <= g <= MAX_GAP + 1:
         raise ValueError(f"g: 1 .. {MAX_GAP + 1} frames back expected, got {g}")
     want, open_ = np.asarray(want, bool), np.asarray(open, bool)
     if want.shape != (n,) or open_.shape != (n,):
         raise ValueError(f"want and open: bool [{n}] expected, got {want.shape} and {open_.shape}")
-    moved = None
-    if field is not None:
-        moved = np.ascontiguousarray(field, np.int32)
-        if int(tile) not in FLOW_TILES or moved.shape != (T, -(-H // int(tile)), -(-W // int(tile)), 2):
-            raise ValueError(f"field: int32 [{T}, ceil({H} / tile), ceil({W} / tile), 2] with a tile of {FLOW_TILES} expected, "
-                             f"got {moved.shape} with tile {tile}")
-    elif shift is not None:
-        moved = np.ascontiguousarray(shift, np.int32)
-        if moved.shape != (T, 2):
-            raise ValueError(f"shift: int32 [{T}, 2] expected, got {moved.shape}")
-    if table_cap is None:
-        frame = np.repeat(np.arange(T), np.diff(off))
-        nw, no = np.bincount(frame[want], minlength=T), np.bincount(frame[open_], minlength=T)
-        pair = int((nw[g:] + no[:T - g]).max()) if T > g else 0
-        table_cap = min(max(MIN_TABLE, _pow2(4 * pair)), _pow2(H * W + 1))
-    pred, ovl, status = _links_gap_call(lab, pix, off, int(table_cap), g, want, open_, moved, tile, off_d)
-    pred, ovl = pred.copy(), ovl.copy()
-    for t in np.nonzero(status)[0]:
-        lo, hi = int(off[t - g]), int(off[t + 1])
-        sub = off[t - g:t + 2] - lo
-        p2, o2, s2 = _links_gap_call(lab[t - g:t + 1], pix, sub, max(MIN_TABLE, _pow2(H * W + 1)), g, want[lo:hi],
-                                     open_[lo:hi], None if moved is None else moved[t - g:t + 1], tile)
-        if s2.any():
-            raise RuntimeError("mseg_cell_links_gap: a table of more than H * W entries reported full")
-        pred[off[t]:off[t + 1]] = p2[sub[g]:]
-        ovl[off[t]:off[t + 1]] = o2[sub[g]:]
-    return pred, ovl
+    return _links(lab, pix, off, table_cap, moved, tile, g, (want, open_), off_d)
 
 
 def close_gaps(lab, pix, off, pred, overlap, min_overlap, G, shift=None, field=None, tile=None):
@@ -736,25 +720,14 @@ def close_gaps(lab, pix, off, pred, overlap, min_overlap, G, shift=None, field=N
 def check_neighbors(r):
     """the rule of ``measure_cells(neighbors=...)``, ``InferWorker.neighbors`` and --neighbors: None, or an int in 1 ..
     MAX_NEIGHBOR_RADIUS"""
-    if r is None:
-        return None
-    try:
-        ok = not isinstance(r, (bool, str, bytes)) and int(r) == r and 1 <= int(r) <= MAX_NEIGHBOR_RADIUS
-    except (TypeError, ValueError, OverflowError):
-        ok = False
-    if not ok:
-        raise ValueError(f"neighbors: None or a whole number of pixels in 1 .. {MAX_NEIGHBOR_RADIUS} expected, got {r!r}")
-    return int(r)
+    return None if r is None else _whole(r, 1, MAX_NEIGHBOR_RADIUS,
+                                         f"neighbors: None or a whole number of pixels in 1 .. {MAX_NEIGHBOR_RADIUS}")
 
 
 def _neighbors_call(lab, pix, off, radius, cap, pair_cap):
     """one ``mseg_cell_neighbors`` call with room for ``pair_cap`` rows, repeated with the exact count if there are more
     -> (ints int64 [9, n], pairs int32 [m, 5], status int32 [T])"""
-    lib = _lib.load()
-    dev = lab.device
-    T, H, W = (int(v) for v in lab.shape)
-    n = int(off[-1])
-    off_d = _offsets_to_device(off, dev)
+    lib, dev, T, H, W, n, off_d = _raw_args(lab, off)
     ws = _workspace(lib.mseg_cell_neighbors_workspace_bytes(T, n, cap), dev,
                     f"mseg_cell_neighbors: no workspace for T = {T}, {n} cells, table {cap}")
     out = torch.zeros((9, max(n, 1)), dtype=torch.int64, device=dev)
@@ -823,12 +796,9 @@ def cell_contacts(mask, radius=8, device=None):
     radius = check_neighbors(radius)
     if radius is None:
         raise ValueError("cell_contacts: a radius in 1 .. 32 is needed")
-    dev = _device(device)
-    with torch.cuda.device(dev):
-        lab, pix = _labels_to_device(mask, dev)
-        off = np.zeros(int(lab.shape[0]) + 1, np.int64)
-        np.cumsum(_frame_counts(lab), out=off[1:])
-        pairs = neighbors_raw(lab, pix, off, radius)[1]
+    st = _Stack(mask, device=device)
+    with torch.cuda.device(st.dev):
+        pairs = neighbors_raw(st.lab, st.pix, st.off, radius)[1]
     return contacts_from_pairs(pairs)
 
 
@@ -845,15 +815,8 @@ def check_spots(thr, scale=2):
     (thr, scale) as ints"""
     if thr is None:
         return None
-    for name, v, top in (("spots", thr, MAX_SPOT_THRESHOLD), ("spot_scale", scale, MAX_SPOT_SCALE)):
-        try:
-            ok = not isinstance(v, (bool, str, bytes)) and int(v) == v and 1 <= int(v) <= top
-        except (TypeError, ValueError, OverflowError):
-            ok = False
-        if not ok:
-            raise ValueError(f"{name}: " + ("None or " if name == "spots" else "") + f"a whole number in 1 .. {top} expected, "
-                             f"got {v!r}")
-    return int(thr), int(scale)
+    return _whole(thr, 1, MAX_SPOT_THRESHOLD, f"spots: None or a whole number in 1 .. {MAX_SPOT_THRESHOLD}"), \
+        _whole(scale, 1, MAX_SPOT_SCALE, f"spot_scale: a whole number in 1 .. {MAX_SPOT_SCALE}")
 
 
 def spot_bound(T, H, W, C=1):
@@ -868,16 +831,11 @@ def spots_raw(lab, pix, off, image, channels, thr, scale, spot_cap=None):
     x): the same bytes from run to run.  ``spot_cap``: room for so many spots per call (default: 4 per cell and 1024 per
     frame and channel); a list that overflowed (the device's status word says so) is never returned: the call is redone
     with room for the count the device reported, at most the worst case ``spot_bound``: the result is always complete."""
-    lib = _lib.load()
-    dev = lab.device
-    T, H, W = (int(v) for v in lab.shape)
-    n = int(off[-1])
-    if image is None or not len(channels):
-        raise ValueError("spots are taken of an image's channels: none given")
+    _need_channels(image is not None and len(channels), "none given", spots=True)
     if check_spots(thr, scale) is None:
         raise ValueError("spots_raw: a threshold is needed")
     thr, scale = check_spots(thr, scale)
-    off_d = _offsets_to_device(off, dev)
+    lib, dev, T, H, W, n, off_d = _raw_args(lab, off)
     counts, bgs, recs, first_ci = [], [], [], 0
     for group in _channel_groups(list(channels)):
         Cg = group[2]
@@ -980,25 +938,13 @@ def cell_spots(mask, img, channels=None, spots=None, spot_scale=2, background=Fa
     checked = check_spots(spots, spot_scale)
     if checked is None:
         raise ValueError("cell_spots: a threshold in 1 .. 65535 grey levels is needed")
-    if img is None:
-        raise ValueError("spots are taken of an image's channels: no image given")
-    dev = _device(device)
-    with torch.cuda.device(dev):
-        lab, pix = _labels_to_device(mask, dev)
-        T, H, W = (int(v) for v in lab.shape)
-        off = np.zeros(T + 1, np.int64)
-        np.cumsum(_frame_counts(lab), out=off[1:])
-        image = _image_to_device(img, (T, H, W), dev)
-        if image is None:
-            raise ValueError("only uint8 / uint16 images are measured")
-        channels = list(range(image[3])) if channels is None else [int(c) for c in channels]
-        if any(c < 0 or c >= image[3] for c in channels):
-            raise ValueError(f"channels {channels} requested, the image has {image[3]}")
-        if not channels:
-            raise ValueError("spots are taken of an image's channels: none is measured")
-        raw = measure_raw(lab, pix, off)
-        records = spots_raw(lab, pix, off, image, channels, *checked)[2]
-    return spots_from_records(records, checked[1], off, raw, channels, background)
+    _need_channels(img is not None, "no image given", spots=True)
+    st = _Stack(mask, img, channels, device)
+    _need_channels(st.channels, "none is measured", spots=True)
+    with torch.cuda.device(st.dev):
+        raw = measure_raw(st.lab, st.pix, st.off)
+        records = spots_raw(st.lab, st.pix, st.off, st.image, st.channels, *checked)[2]
+    return spots_from_records(records, checked[1], st.off, raw, st.channels, background)
 
 
 def _spot_sums(records, off, n_channels):
@@ -1022,17 +968,8 @@ def _spot_sums(records, off, n_channels):
 def check_profile(bins):
     """the rule of ``measure_cells(profile=...)``, ``InferWorker.profile`` and --profile: None = off -> None; else a whole
     number of bins in 2 .. 32 -> an int"""
-    if bins is None:
-        return None
-    try:
-        ok = not isinstance(bins, (bool, str, bytes)) and int(bins) == bins and \
-            MIN_PROFILE_BINS <= int(bins) <= MAX_PROFILE_BINS
-    except (TypeError, ValueError, OverflowError):
-        ok = False
-    if not ok:
-        raise ValueError(f"profile: None or a whole number of bins in {MIN_PROFILE_BINS} .. {MAX_PROFILE_BINS} expected, "
-                         f"got {bins!r}")
-    return int(bins)
+    return None if bins is None else _whole(bins, MIN_PROFILE_BINS, MAX_PROFILE_BINS, "profile: None or a whole number of bins in "
+                                            f"{MIN_PROFILE_BINS} .. {MAX_PROFILE_BINS}")
 
 
 def profile_direction(orientation):
@@ -1075,15 +1012,11 @@ def profile_raw(lab, pix, off, image, channels, bbox, dirs, bins, area=None):
     ``measure_raw``.  The call has no status word: a cell whose bins do not add up to its area has pixels outside the box
     given for it, which raises here.  ``area``: the areas ``measure_raw`` reported (raw["shape"][0]); None: they are measured
     here."""
-    lib = _lib.load()
-    dev = lab.device
-    T, H, W = (int(v) for v in lab.shape)
     n = int(off[-1])
     N = check_profile(bins)
     if N is None:
         raise ValueError("profile_raw: a number of bins is needed")
-    if image is None or not len(channels):
-        raise ValueError("profiles are taken of an image's channels: none given")
+    _need_channels(image is not None and len(channels), "none given", profiles=True)
     dirs = np.ascontiguousarray(dirs, np.int32)
     if dirs.shape != (n, 2):
         raise ValueError(f"dirs: int32 [{n}, 2] expected, got {dirs.shape}")
@@ -1093,7 +1026,7 @@ def profile_raw(lab, pix, off, image, channels, bbox, dirs, bins, area=None):
         return np.zeros((N, 0), np.uint32), np.zeros((len(channels), N, 0), np.uint64), np.zeros((2, 0), np.int64)
     if area is None:
         area = measure_raw(lab, pix, off)["shape"][0]
-    off_d = _offsets_to_device(off, dev)
+    lib, dev, T, H, W, n, off_d = _raw_args(lab, off)
     bbox_d = torch.from_numpy(np.ascontiguousarray(bbox, np.int32).reshape(n, 4)).to(dev)
     dirs_d = torch.from_numpy(dirs).to(dev)
     count, extent, sums = None, None, []
@@ -1206,26 +1139,14 @@ def cell_profiles(mask, img, channels=None, bins=16, device=None):
     bins = check_profile(bins)
     if bins is None:
         raise ValueError("cell_profiles: a number of bins in 2 .. 32 is needed")
-    if img is None:
-        raise ValueError("profiles are taken of an image's channels: no image given")
-    dev = _device(device)
-    with torch.cuda.device(dev):
-        lab, pix = _labels_to_device(mask, dev)
-        T, H, W = (int(v) for v in lab.shape)
-        off = np.zeros(T + 1, np.int64)
-        np.cumsum(_frame_counts(lab), out=off[1:])
-        image = _image_to_device(img, (T, H, W), dev)
-        if image is None:
-            raise ValueError("only uint8 / uint16 images are measured")
-        channels = list(range(image[3])) if channels is None else [int(c) for c in channels]
-        if any(c < 0 or c >= image[3] for c in channels):
-            raise ValueError(f"channels {channels} requested, the image has {image[3]}")
-        if not channels:
-            raise ValueError("profiles are taken of an image's channels: none is measured")
-        raw = measure_raw(lab, pix, off)
-        count, sums, _ = profile_raw(lab, pix, off, image, channels, raw["bbox"], _cell_directions(raw), bins,
+    _need_channels(img is not None, "no image given", profiles=True)
+    st = _Stack(mask, img, channels, device)
+    _need_channels(st.channels, "none is measured", profiles=True)
+    with torch.cuda.device(st.dev):
+        raw = measure_raw(st.lab, st.pix, st.off)
+        count, sums, _ = profile_raw(st.lab, st.pix, st.off, st.image, st.channels, raw["bbox"], _cell_directions(raw), bins,
                                      raw["shape"][0])
-    return profiles_from_raw(off, raw["shape"][0], channels, count, sums)
+    return profiles_from_raw(st.off, raw["shape"][0], st.channels, count, sums)
 
 
 def assemble_tracks(frame, label, pred, overlap, min_overlap=1, gap=None):
@@ -1309,129 +1230,215 @@ def _neighborhood(v):
             contact_max]
 
 
+# ---- the column families ----------------------------------------------------------------------------------------------------
+# A family is two functions.  ``names(channels, percentiles)``: its columns.  ``rows(tb)``: called once per table with the
+# arguments of ``table_from_sums`` (and, as Python integers, ``tb.first``: the offsets, ``tb.slots`` = n, ``tb.sh``: raw["shape"]);
+# it prepares what it can for all cells and returns ``row(t, s)`` -> the values of the cell in slot s of frame t, one per name.
+# Python integers and one fp64 division or sqrt per value: n * sq - sv * sv passes int64.
+
+def _planes(ints, count, slots):
+    """the integers [count, n] of a ``*_raw`` call as Python integers, plane by plane"""
+    return [[int(v) for v in plane] for plane in np.asarray(ints).reshape(count, slots)]
+
+
+def _shape_rows(tb):
+    """frame, label, area = n, the centroid sy / n, sx / n, the box of ``measure_raw``, the axes and the orientation of ``_axes``,
+    and touches_border: the box reaches an edge of the H x W frame"""
+    sh, first, H, W = tb.sh, tb.first, tb.H, tb.W
+    boxes = np.asarray(tb.raw["bbox"]).tolist()
+    def row(t, s):
+        n = sh[0][s]
+        major, minor, orientation = _axes(n, sh[1][s], sh[2][s], sh[3][s], sh[4][s], sh[5][s])
+        r0, c0, r1, c1 = boxes[s]
+        return [t, s - first[t] + 1, n, sh[1][s] / n, sh[2][s] / n, r0, c0, r1, c1, major, minor, orientation,
+                bool(r0 == 0 or c0 == 0 or r1 == H or c1 == W)]
+    return row
+
+
+def _channel_rows(tb):
+    """per measured channel, from the sums of ``measure_raw``: mean = sv / n, std = sqrt((n sq - sv^2) / n^2), min, max, sum
+    = sv, and bg_mean, the mean over the frame's label-0 pixels (NaN for a frame without background)"""
+    raw, sh, C = tb.raw, tb.sh, range(len(tb.channels))
+    if not C:
+        return lambda t, s: []
+    sums, minmax, bg_sums = (np.asarray(raw[key]).tolist() for key in ("ch_sums", "ch_minmax", "bg_sums"))
+    bg = [[bg_sums[1][t][ci] / bg_sums[0][t][ci] if bg_sums[0][t][ci] else float("nan") for ci in C]
+          for t in range(len(tb.first) - 1)]
+    def row(t, s):
+        n, out = sh[0][s], []
+        for ci in C:
+            sv, sq = sums[0][ci][s], sums[1][ci][s]
+            out += [sv / n, math.sqrt((n * sq - sv * sv) / (n * n)), minmax[0][ci][s], minmax[1][ci][s], sv, bg[t][ci]]
+        return out
+    return row
+
+
+def _link_rows(tb):
+    """``links`` = (pred, overlap): pred_label and overlap; track_id and parent_track are assembled over the whole table"""
+    pred, overlap = ([int(v) for v in side] for side in tb.links)
+    return lambda t, s: [pred[s], overlap[s], 0, 0]
+
+
+def _drift_rows(tb):
+    """``shift``: int [T, 2], the (dy, dx) of every frame against its predecessor the links were taken under (row 0 ignored):
+    drift_y / drift_x, the shifts summed up to the frame, and centroid_y_reg / centroid_x_reg, the centroid minus them"""
+    sh = tb.sh
+    shift = np.asarray(tb.shift, np.int64).reshape(len(tb.first) - 1, 2).copy()
+    shift[0] = 0
+    total = [(int(a), int(b)) for a, b in np.cumsum(shift, axis=0)]      # against frame 0
+    def row(t, s):
+        (dy, dx), n = total[t], sh[0][s]
+        return [dy, dx, sh[1][s] / n - dy, sh[2][s] / n - dx]
+    return row
+
+
+def _flow_rows(tb):
+    """``field`` with ``tile``: int [T, ty, tx, 2], the field of ``pick_flow`` the links were taken under: flow_y / flow_x, the
+    field value of the tile that holds the pixel (floor(centroid_y), floor(centroid_x)), 0 in frame 0"""
+    sh, tile = tb.sh, int(tb.tile)
+    field = np.asarray(tb.field, np.int64).copy()
+    field[0] = 0
+    field = field.tolist()
+    return lambda t, s: field[t][sh[1][s] // sh[0][s] // tile][sh[2][s] // sh[0][s] // tile]
+
+
+def _gap_rows(tb):
+    """``gaps``: int [n], the pred_gap of ``close_gaps`` (with its pred and overlap as ``links``): pred_gap; the tracks are
+    assembled over the gaps"""
+    gaps = [int(v) for v in tb.gaps]
+    return lambda t, s: [gaps[s]]
+
+
+def _hull_rows(tb):
+    """``hull``: int [10, n], the integers of ``hull_raw``: perimeter (exposed pixel edges), convex_area = hull_area2 / 2,
+    solidity = area / convex_area, feret_max = sqrt(feret2), feret_min = num / sqrt(den2), feret_angle = atan2(bx - ax, by -
+    ay) in (-pi/2, pi/2] from the row axis, and the chord's end points (``_outline``)"""
+    sh, hl = tb.sh, _planes(tb.hull, 10, tb.slots)
+    return lambda t, s: _outline(sh[0][s], [plane[s] for plane in hl])
+
+
+def _midline_rows(tb):
+    """``midline``: int [12, n], the integers of ``midline_raw``: skeleton_pixels = skel_n, skeleton_length = n_orth + sqrt(2)
+    n_diag, skeleton_ends, skeleton_branches, midline_length = skeleton_length + sqrt(e0_d2) + sqrt(e1_d2) - 1 where the
+    skeleton is one open chain (n_end == 2 and n_branch == 0) or one pixel, NaN otherwise, midline_width = area /
+    midline_length, and the two end points, 0 where there are none (``_midline``)"""
+    sh, ml = tb.sh, _planes(tb.midline, 12, tb.slots)
+    return lambda t, s: _midline(sh[0][s], [plane[s] for plane in ml])
+
+
+def _percentile_rows(tb):
+    """``order_stats``: (percentiles, values uint32 [2 P, C, n], bg_values uint32 [2 P, T, C]): the integers of
+    ``order_stats_raw`` for the ranks of ``percentile_ranks`` (cell counts: raw["shape"][0], background counts:
+    raw["bg_sums"][0]): p{P}_ch{c} = ``percentile_value`` of the two order statistics, and bg_p{P}_ch{c} (NaN without
+    background)"""
+    pct, C, T = tb.pct, len(tb.channels), len(tb.first) - 1
+    values = np.asarray(tb.order_stats[1]).reshape(2 * len(pct), C, tb.slots)
+    bg_values = np.asarray(tb.order_stats[2]).reshape(2 * len(pct), T, C)
+    bg_n = np.asarray(tb.raw["bg_sums"][0]).astype(np.int64)                                 # [T, C]
+    g = percentile_ranks(np.asarray(tb.raw["shape"][0]).astype(np.int64), pct)[1]             # [P, n]
+    cell_p = percentile_value(values[0::2], values[1::2], g[:, None, :]).tolist()             # [P, C, n], Python floats
+    bg_p = np.where(bg_n[None] > 0, percentile_value(bg_values[0::2], bg_values[1::2], percentile_ranks(bg_n, pct)[1]),
+                    np.nan).tolist()
+    order = [(i, ci) for ci in range(C) for i in range(len(pct))]
+    return lambda t, s: [cell_p[i][ci][s] for i, ci in order] + [bg_p[i][t][ci] for i, ci in order]
+
+
+def _neighbor_rows(tb):
+    """``neighbors``: int [9, n], the integers of ``neighbors_raw``: contact_length = contact_edges, border_length =
+    border_edges, contact_fraction = contact_edges / (contact_edges + border_edges + free_edges), n_touching = n_touch,
+    n_neighbors = n_near, nn_label, nn_distance = sqrt(nn_d2) and nn_gap = nn_distance - 1 (both NaN where no cell lies within
+    the radius, nn_label then 0), contact_label and contact_max = contact_label_edges (both 0 where no cell shares an edge)
+    (``_neighborhood``)"""
+    nbl = _planes(tb.neighbors, 9, tb.slots)
+    return lambda t, s: _neighborhood([plane[s] for plane in nbl])
+
+
+def _spot_rows(tb):
+    """``spots``: (scale, cell_count int32 [C, n], bg_count int32 [T, C], records), the scale and the three results of
+    ``spots_raw``: per measured channel n_spots_ch{c} = cell_count, spot_max_ch{c} = the largest D among the cell's records /
+    16^(2 scale) (NaN without a spot), spot_sum_ch{c} = the exact integer sum of their D / 16^(2 scale) (0 without),
+    bg_spots_ch{c} = bg_count of the frame"""
+    scale, cell_count, bg_count, records = tb.spots
+    C, unit = range(len(tb.channels)), 1 << (8 * int(scale))
+    count = np.asarray(cell_count).reshape(len(C), tb.slots).tolist()
+    bg = np.asarray(bg_count).reshape(len(tb.first) - 1, len(C)).tolist()
+    found = _spot_sums(records, tb.first, len(C))
+    def row(t, s):
+        out = []
+        for ci in C:
+            top, d_sum = found.get((ci, s), (None, 0))
+            out += [count[ci][s], top / unit if top is not None else float("nan"), d_sum / unit, bg[t][ci]]
+        return out
+    return row
+
+
+def _profile_rows(tb):
+    """``profile``: (count [N, n], sums [C, N, n], extent [2, n]), the integers of ``profile_raw``: axis_extent = ``axis_extent``
+    of the cell's extreme projections and, per measured channel, pole_mid_ratio_ch{c}, pole_asym_ch{c} and profile_peak_ch{c}
+    = ``profile_columns`` of the cell's bins"""
+    count, sums, extent = tb.profile
+    q = np.asarray(extent).astype(np.int64).reshape(2, tb.slots)
+    length = ((q[1] - q[0]) / PROFILE_UNIT + 1).tolist()                                     # ``axis_extent``, all cells at once
+    bins = np.asarray(count).shape[0]                             # N: a stack without a cell still has its bins
+    per_channel = [profile_columns(count, plane)                                              # [C][3][n]
+                   for plane in np.asarray(sums).reshape(len(tb.channels), bins, tb.slots)]
+    return lambda t, s: [length[s]] + [col[s] for cols in per_channel for col in cols]
+
+
+def _per_channel(stencil):
+    return lambda channels, pct: [name.format(c=int(c)) for c in channels for name in stencil]
+
+
+_FAMILIES = (          # (the switch of ``columns``, names, rows) in the order of the table's columns
+    (None, lambda channels, pct: SHAPE_COLUMNS, _shape_rows),
+    (None, _per_channel(CHANNEL_COLUMNS), _channel_rows),
+    ("link", lambda channels, pct: LINK_COLUMNS, _link_rows),
+    ("drift", lambda channels, pct: DRIFT_COLUMNS, _drift_rows),
+    ("flow", lambda channels, pct: FLOW_COLUMNS, _flow_rows),
+    ("gap", lambda channels, pct: GAP_COLUMNS, _gap_rows),
+    ("hull", lambda channels, pct: HULL_COLUMNS, _hull_rows),
+    ("midline", lambda channels, pct: MIDLINE_COLUMNS, _midline_rows),
+    ("percentiles", lambda channels, pct: [name.format(p=int(q), c=int(c)) for name in PERCENTILE_COLUMNS for c in channels
+                                           for q in pct], _percentile_rows),
+    ("neighbors", lambda channels, pct: NEIGHBOR_COLUMNS, _neighbor_rows),
+    ("spots", _per_channel(SPOT_COLUMNS), _spot_rows),
+    ("profile", lambda channels, pct: ['axis_extent'] + _per_channel(PROFILE_COLUMNS)(channels, pct), _profile_rows),
+)
+
+
 def table_from_sums(off, H, W, raw, channels=(), links=None, min_overlap=1, shift=None, hull=None, midline=None,
                     order_stats=None, neighbors=None, spots=None, field=None, tile=None, gaps=None, profile=None):
     """the DataFrame from the integer sums of ``measure_raw`` (and ``links`` = (pred, overlap) or None); host arithmetic in
-    Python integers and fp64.  ``shift``: int [T, 2], the (dy, dx) of every frame against its predecessor the links were
-    taken under (row 0 ignored), or None: with it the drift columns follow the link columns.  ``hull``: int [10, n], the
-    integers of ``hull_raw``, or None: with it the table ends with the outline columns: perimeter (exposed pixel edges),
-    convex_area = hull_area2 / 2, solidity = area / convex_area, feret_max = sqrt(feret2), feret_min = num / sqrt(den2),
-    feret_angle = atan2(bx - ax, by - ay) in (-pi/2, pi/2] from the row axis, and the chord's end points.  ``midline``: int
-    [12, n], the integers of ``midline_raw``, or None: with it the table ends with the midline columns: skeleton_pixels =
-    skel_n, skeleton_length = n_orth + sqrt(2) n_diag, skeleton_ends, skeleton_branches, midline_length = skeleton_length +
-    sqrt(e0_d2) + sqrt(e1_d2) - 1 where the skeleton is one open chain (n_end == 2 and n_branch == 0) or one pixel, NaN
-    otherwise, midline_width = area / midline_length, and the two end points (0 where there are none).  ``order_stats``:
-    (percentiles, values uint32 [2 P, C, n], bg_values uint32 [2 P, T, C]): the integers of ``order_stats_raw`` for the ranks
-    of ``percentile_ranks`` (cell counts: raw["shape"][0], background counts: raw["bg_sums"][0]), or None: with it the table
-    ends with p{P}_ch{c} = ``percentile_value`` of the two order statistics, and bg_p{P}_ch{c} (NaN without background).
-    ``neighbors``: int [9, n], the integers of ``neighbors_raw``, or None: with it the table ends with the neighbourhood
-    columns: contact_length = contact_edges, border_length = border_edges, contact_fraction = contact_edges / (contact_edges
-    + border_edges + free_edges), n_touching = n_touch, n_neighbors = n_near, nn_label, nn_distance = sqrt(nn_d2) and nn_gap =
-    nn_distance - 1 (both NaN where no cell lies within the radius, nn_label then 0), contact_label and contact_max =
-    contact_label_edges (both 0 where no cell shares an edge).  ``spots``: (scale, cell_count int32 [C, n], bg_count int32
-    [T, C], records), the scale and the three results of ``spots_raw``, or None: with it the table ends with four columns per
-    measured channel: n_spots_ch{c} = cell_count, spot_max_ch{c} = the largest D among the cell's records / 16^(2 scale) (NaN
-    without a spot), spot_sum_ch{c} = the exact integer sum of their D / 16^(2 scale) (0 without), bg_spots_ch{c} = bg_count
-    of the frame.  ``field`` with ``tile``: int [T, ty, tx, 2], the field of ``pick_flow`` the links were taken under (needs
-    ``shift``), or None: with it flow_y / flow_x follow the drift columns: the field value of the tile that holds the pixel
-    (floor(centroid_y), floor(centroid_x)), 0 in frame 0.  ``gaps``: int [n], the pred_gap of ``close_gaps`` (with its pred and
-    overlap as ``links``), or None: with it pred_gap follows the link, drift and flow columns and the tracks are assembled
-    over the gaps.  ``profile``: (count [N, n], sums [C, N, n], extent [2, n]), the integers of ``profile_raw``, or None: with it
-    the table ends with axis_extent = ``axis_extent`` of the cell's extreme projections and, per measured channel,
-    pole_mid_ratio_ch{c}, pole_asym_ch{c} and profile_peak_ch{c} = ``profile_columns`` of the cell's bins"""
-    off = np.asarray(off, np.int64)
-    area = raw["shape"][0]
+    Python integers and fp64.  Every further argument is the integers of one column family, or None for a table without it;
+    what it holds and what becomes of it stands with the family (``_drift_rows`` for ``shift``, ``_flow_rows`` for ``field``
+    with ``tile``, which needs ``shift``, ``_gap_rows`` for ``gaps``, ``_hull_rows``, ``_midline_rows``, ``_percentile_rows`` for
+    ``order_stats``, ``_neighbor_rows``, ``_spot_rows``, ``_profile_rows``).  The columns are those of ``columns`` in its order,
+    whichever families are given; a row that does not bring exactly one value per column raises."""
     if field is not None and shift is None:
         raise ValueError("the flow columns follow the drift columns: field needs shift")
     pct = check_percentiles(order_stats[0]) if order_stats is not None else ()
-    if pct and not len(channels):
-        raise ValueError("percentiles are taken of an image's channels: none is measured")
-    if spots is not None and not len(channels):
-        raise ValueError("spots are taken of an image's channels: none is measured")
-    if profile is not None and not len(channels):
-        raise ValueError("profiles are taken of an image's channels: none is measured")
-    rows = {c: [] for c in columns(channels, links is not None, shift is not None, hull is not None, midline is not None, pct,
-                                   neighbors is not None, spots is not None, field is not None, gaps is not None,
-                                   profile is not None)}
-    if profile is not None:
-        pf_q = np.asarray(profile[2]).astype(np.int64).reshape(2, len(area))
-        pf_len = ((pf_q[1] - pf_q[0]) / PROFILE_UNIT + 1).tolist()                            # ``axis_extent``, all cells at once
-        pf_bins = np.asarray(profile[0]).shape[0]                 # N: a stack without a cell still has its bins
-        pf_cols = [profile_columns(profile[0], plane)                                         # [C][3][n]
-                   for plane in np.asarray(profile[1]).reshape(len(channels), pf_bins, len(area))]
-    if field is not None:
-        field = np.asarray(field, np.int64).copy()
-        field[0] = 0
-        field, tile = field.tolist(), int(tile)
-    if spots is not None:
-        sp_unit = 1 << (8 * int(spots[0]))
-        sp_n = np.asarray(spots[1]).reshape(len(channels), len(area)).tolist()
-        sp_bg = np.asarray(spots[2]).reshape(len(off) - 1, len(channels)).tolist()
-        sp_acc = _spot_sums(spots[3], off, len(channels))
-    if neighbors is not None:
-        nbl = [[int(v) for v in plane] for plane in np.asarray(neighbors).reshape(9, len(area))]
-    if pct:
-        vals = np.asarray(order_stats[1]).reshape(2 * len(pct), len(channels), len(area))
-        bgv = np.asarray(order_stats[2]).reshape(2 * len(pct), len(off) - 1, len(channels))
-        bg_n = np.asarray(raw["bg_sums"][0]).astype(np.int64)                                # [T, C]
-        g = percentile_ranks(np.asarray(area).astype(np.int64), pct)[1]                       # [P, n]
-        cell_p = percentile_value(vals[0::2], vals[1::2], g[:, None, :])                      # [P, C, n]
-        bg_p = np.where(bg_n[None] > 0, percentile_value(bgv[0::2], bgv[1::2], percentile_ranks(bg_n, pct)[1]), np.nan)
-        cell_p, bg_p = cell_p.tolist(), bg_p.tolist()                                         # Python floats, as every column
-    if hull is not None:
-        hl = [[int(v) for v in plane] for plane in np.asarray(hull).reshape(10, len(area))]
-    if midline is not None:
-        ml = [[int(v) for v in plane] for plane in np.asarray(midline).reshape(12, len(area))]
-    if shift is not None:
-        shift = np.asarray(shift, np.int64).reshape(len(off) - 1, 2).copy()
-        shift[0] = 0
-        total = [(int(a), int(b)) for a, b in np.cumsum(shift, axis=0)]      # against frame 0
-    sh = [[int(v) for v in plane] for plane in raw["shape"]]
-    for t in range(len(off) - 1):
-        bg = []
-        for ci in range(len(channels)):
-            cnt = int(raw["bg_sums"][0, t, ci])
-            bg.append(int(raw["bg_sums"][1, t, ci]) / cnt if cnt else float("nan"))
-        for s in range(int(off[t]), int(off[t + 1])):
-            n = sh[0][s]
-            if n == 0:
+    _need_channels(len(channels), "none is measured", percentiles=pct, spots=spots is not None, profiles=profile is not None)
+    given = dict(link=links is not None, drift=shift is not None, hull=hull is not None, midline=midline is not None,
+                 percentiles=pct, neighbors=neighbors is not None, spots=spots is not None, flow=field is not None,
+                 gap=gaps is not None, profile=profile is not None)
+    cols = columns(channels, **given)
+    area = raw["shape"][0]
+    first, slots, sh = [int(v) for v in off], len(area), _planes(raw["shape"], 6, len(area))
+    tb = types.SimpleNamespace(**locals())      # the arguments, pct, first, slots and sh: what the families read
+    families = [rows(tb) for key, _, rows in _FAMILIES if given.get(key, True)]
+    lists = [[] for _ in cols]
+    for t in range(len(first) - 1):
+        for s in range(first[t], first[t + 1]):
+            if sh[0][s] == 0:
                 continue
-            major, minor, orientation = _axes(n, sh[1][s], sh[2][s], sh[3][s], sh[4][s], sh[5][s])
-            r0, c0, r1, c1 = (int(v) for v in raw["bbox"][s])
-            vals = [t, s - int(off[t]) + 1, n, sh[1][s] / n, sh[2][s] / n, r0, c0, r1, c1, major, minor, orientation,
-                    bool(r0 == 0 or c0 == 0 or r1 == H or c1 == W)]
-            for ci in range(len(channels)):
-                sv, sq = int(raw["ch_sums"][0, ci, s]), int(raw["ch_sums"][1, ci, s])
-                vals += [sv / n, math.sqrt((n * sq - sv * sv) / (n * n)), int(raw["ch_minmax"][0, ci, s]),
-                         int(raw["ch_minmax"][1, ci, s]), sv, bg[ci]]
-            if links is not None:
-                vals += [int(links[0][s]), int(links[1][s]), 0, 0]
-            if shift is not None:
-                vals += [total[t][0], total[t][1], sh[1][s] / n - total[t][0], sh[2][s] / n - total[t][1]]
-            if field is not None:
-                vals += field[t][sh[1][s] // n // tile][sh[2][s] // n // tile]
-            if gaps is not None:
-                vals += [int(gaps[s])]
-            if hull is not None:
-                vals += _outline(n, [plane[s] for plane in hl])
-            if midline is not None:
-                vals += _midline(n, [plane[s] for plane in ml])
-            if pct:
-                vals += [cell_p[i][ci][s] for ci in range(len(channels)) for i in range(len(pct))]
-                vals += [bg_p[i][t][ci] for ci in range(len(channels)) for i in range(len(pct))]
-            if neighbors is not None:
-                vals += _neighborhood([plane[s] for plane in nbl])
-            if spots is not None:
-                for ci in range(len(channels)):
-                    top, total = sp_acc.get((ci, s), (None, 0))
-                    vals += [sp_n[ci][s], top / sp_unit if top is not None else float("nan"), total / sp_unit, sp_bg[t][ci]]
-            if profile is not None:
-                vals += [pf_len[s]]
-                for ci in range(len(channels)):
-                    vals += [col[s] for col in pf_cols[ci]]
-            for c, v in zip(rows, vals):
-                rows[c].append(v)
-    df = pd.DataFrame(rows, columns=list(rows))
+            vals = []
+            for row in families:
+                vals += row(t, s)
+            if len(vals) != len(cols):
+                raise RuntimeError(f"cell table: {len(vals)} values for the {len(cols)} columns of the cell in slot {s}")
+            for column, v in zip(lists, vals):
+                column.append(v)
+    df = pd.DataFrame(dict(zip(cols, lists)), columns=cols)
     assert int((area > 0).sum()) == len(df)
     if links is not None:
         df["track_id"], df["parent_track"] = assemble_tracks(df["frame"], df["label"], df["pred_label"], df["overlap"],
@@ -1538,39 +1545,18 @@ def measure_cells(mask, img=None, channels=None, link=True, min_overlap=1, devic
     neighbors = check_neighbors(neighbors)
     spots = check_spots(spots, spot_scale)
     profile = check_profile(profile)
-    if profile is not None and img is None:
-        raise ValueError("profiles are taken of an image's channels: no image given")
-    if percentiles and img is None:
-        raise ValueError("percentiles are taken of an image's channels: no image given")
-    if spots is not None and img is None:
-        raise ValueError("spots are taken of an image's channels: no image given")
+    _need_channels(img is not None, "no image given", profiles=profile is not None, percentiles=percentiles,
+                   spots=spots is not None)
     if drift is not None and not link:
         raise ValueError("drift changes how cells are linked: it needs link=True")
     gap = check_gap(gap)
     if gap is not None and not link:
         raise ValueError("gap closes gaps in the links: it needs link=True")
-    dev = _device(device)
-    with torch.cuda.device(dev):
-        lab, pix = _labels_to_device(mask, dev)
-        T, H, W = (int(v) for v in lab.shape)
-        off = np.zeros(T + 1, np.int64)
-        np.cumsum(_frame_counts(lab), out=off[1:])
-        image = None
-        if img is not None:
-            image = _image_to_device(img, (T, H, W), dev)
-            if image is None:
-                raise ValueError("only uint8 / uint16 images are measured")
-            channels = list(range(image[3])) if channels is None else [int(c) for c in channels]
-            if any(c < 0 or c >= image[3] for c in channels):
-                raise ValueError(f"channels {channels} requested, the image has {image[3]}")
-        else:
-            channels = []
-        if percentiles and not channels:
-            raise ValueError("percentiles are taken of an image's channels: none is measured")
-        if spots is not None and not channels:
-            raise ValueError("spots are taken of an image's channels: none is measured")
-        if profile is not None and not channels:
-            raise ValueError("profiles are taken of an image's channels: none is measured")
+    st = _Stack(mask, img, channels, device)
+    lab, pix, off, image, channels = st.lab, st.pix, st.off, st.image, st.channels
+    _need_channels(channels, "none is measured", percentiles=percentiles, spots=spots is not None,
+                   profiles=profile is not None)
+    with torch.cuda.device(st.dev):
         raw = measure_raw(lab, pix, off, image, channels)
         shift = pick_drift(drift_raw(lab, pix, off, drift)) if drift is not None else None
         field = pick_flow(flow_raw(lab, pix, off, shift, flow, flow_tile), shift) if flow is not None else None
@@ -1593,7 +1579,7 @@ def measure_cells(mask, img=None, channels=None, link=True, min_overlap=1, devic
         foci = (spots[1],) + spots_raw(lab, pix, off, image, channels, *spots) if spots is not None else None
         bins = profile_raw(lab, pix, off, image, channels, raw["bbox"], _cell_directions(raw), profile,
                            raw["shape"][0]) if profile is not None else None
-    return table_from_sums(off, H, W, raw, channels, links, min_overlap, shift, outline, skel, stats, near, foci, field,
+    return table_from_sums(off, st.H, st.W, raw, channels, links, min_overlap, shift, outline, skel, stats, near, foci, field,
                            flow_tile if field is not None else None, gaps, bins)
 
 

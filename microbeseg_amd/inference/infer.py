@@ -890,17 +890,14 @@ class InferWorker(QObject):
         the outline columns; with ``self.midline`` set, with the midline columns; with ``self.percentiles`` set, with the
         percentile columns; with ``self.neighbors`` set, with the neighbourhood columns; with ``self.spots`` set, with the
         spot columns at ``self.spot_scale``; with ``self.profile`` set, with the profile columns of that many bins. """
-        from .cells import measure_cells
+        from .cells import channel_stems, measure_cells
         df = measure_cells(results, img, link=True, min_overlap=self.min_overlap, device=self.device, drift=self.drift,
                            hull=self.hull, midline=self.midline, percentiles=self.percentiles, neighbors=self.neighbors,
                            spots=self.spots, spot_scale=self.spot_scale, flow=self.flow, flow_tile=self.flow_tile,
                            gap=self.gap, profile=self.profile)
         if img is not None and channels is not None:      # the view holds the chosen channels only: name them by source
             names = {f'{k}_ch{i}': f'{k}_ch{int(c)}' for i, c in reversed(list(enumerate(channels)))
-                     for k in ('mean', 'std', 'min', 'max', 'sum', 'bg_mean') +
-                     tuple(f'{b}p{int(q)}' for q in (self.percentiles or ()) for b in ('', 'bg_')) +
-                     (('n_spots', 'spot_max', 'spot_sum', 'bg_spots') if self.spots is not None else ()) +
-                     (('pole_mid_ratio', 'pole_asym', 'profile_peak') if self.profile is not None else ())}
+                     for k in channel_stems(self.percentiles or (), self.spots is not None, self.profile is not None)}
             df = df.rename(columns=names)
         return df
 

@@ -528,6 +528,64 @@ def test_two_runs_give_identical_bytes(images_a):
     pd.testing.assert_frame_equal(a, b, check_exact=True)
 
 
+# ---- every family at once --------------------------------------------------------------------------------------------------------
+def drifting_grid():
+    """uint16 [3, 70, 131]: 4 x 5 ragged cells that drift by (1, -2) per frame, two of them touching; cell 8 is missed in the
+    middle frame.  With it a [3, 70, 131, 3] uint16 image, foci on some cells, handed over as the strided [T, 3, H, W] view"""
+    rng = np.random.default_rng(12)
+    lab = np.zeros((3, 70, 131), np.uint16)
+    base = rng.integers(0, 300, (3, 70, 131, 3)).astype(np.uint16)
+    for t in range(3):
+        for j in range(4):
+            for i in range(5):
+                l, y, x = 5 * j + i + 1, 4 + 16 * j + t, 12 + 24 * i - 2 * t
+                if (t, l) == (1, 8):
+                    continue
+                lab[t, y:y + 9, x:x + (24 if l == 12 else 15)] = l
+                lab[t, y, x:x + 1 + l % 4] = 0                       # ragged corners: no cell is its own hull
+                lab[t, y + 8, x + 10 - l % 3:x + 15] = 0
+                if l % 3 == 0:
+                    base[t, y + 4, x + 3 + l % 5, :] += 40000 + 100 * l
+    return lab, np.moveaxis(base, -1, 1)
+
+
+def test_every_family_at_once_equals_every_family_alone():
+    """one measure_cells call with every column family on: the columns of ``columns``, and under every family's columns what
+    a call with that family alone returns (the single-family calls are pinned to the restatements by their own files).
+    The link columns hold what link, drift, flow and gap make of them together, so they are compared with a call with
+    these four on and no other family; pred_gap is compared with link and gap alone as well."""
+    from microbeseg_amd.inference import cells
+    lab, img = drifting_grid()
+    assert not img.flags["C_CONTIGUOUS"] and img.shape == (3, 3, 70, 131)
+    ch, motion = [0, 2], dict(drift=4, flow=2, flow_tile=64, gap=1)
+    everything = dict(motion, hull=True, midline=True, percentiles=(5, 50), neighbors=3, spots=500, profile=4)
+    df = cells.measure_cells(lab, img, ch, **everything)
+    assert list(df.columns) == cells.columns(ch, True, True, True, True, (5, 50), True, True, True, True, True)
+    assert len(df) == 59 and (df["pred_gap"] == 2).sum() == 1 and df["drift_x"].min() == -4
+    assert df[[f"n_spots_ch{c}" for c in ch]].to_numpy().sum() >= 10
+
+    def per_channel(stencil):
+        return [name.format(c=c) for c in ch for name in stencil]
+    alone = [
+        (cells.SHAPE_COLUMNS, dict(link=False)),
+        (per_channel(cells.CHANNEL_COLUMNS), dict(img=img, channels=ch, link=False)),
+        (cells.LINK_COLUMNS + cells.GAP_COLUMNS, motion),
+        (cells.DRIFT_COLUMNS, dict(drift=4)),
+        (cells.FLOW_COLUMNS, dict(drift=4, flow=2, flow_tile=64)),
+        (cells.GAP_COLUMNS, dict(gap=1)),
+        (cells.HULL_COLUMNS, dict(link=False, hull=True)),
+        (cells.MIDLINE_COLUMNS, dict(link=False, midline=True)),
+        ([name.format(p=p, c=c) for name in cells.PERCENTILE_COLUMNS for c in ch for p in (5, 50)],
+         dict(img=img, channels=ch, link=False, percentiles=(5, 50))),
+        (cells.NEIGHBOR_COLUMNS, dict(link=False, neighbors=3)),
+        (per_channel(cells.SPOT_COLUMNS), dict(img=img, channels=ch, link=False, spots=500)),
+        (["axis_extent"] + per_channel(cells.PROFILE_COLUMNS), dict(img=img, channels=ch, link=False, profile=4)),
+    ]
+    for cols, switches in alone:
+        one = cells.measure_cells(lab, **switches)
+        assert one[cols].equals(df[cols]), switches
+
+
 # ---- command line ----------------------------------------------------------------------------------------------------------------
 def test_infer_script_cells_end_to_end(tmp_path):
     import subprocess

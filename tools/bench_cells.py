@@ -3,7 +3,7 @@
 the bytes each has to move, the all-in time of measure_cells, and the numpy restatement (tests/cells_ref.py) on one frame
 for one host core.  Synthetic stack as in tools/bench_analysis.py: 2048^2 frames of 4 x 4 synthetic tiles with 150 cells
 each (about 2400 cells per frame), uint16 labels, a 2-channel uint16 image.  Prints one JSON line at the end.  GPU box only.
-  python tools/bench_cells.py [--frames 16] [--reps 5]"""
+  python tools/bench_cells.py [--frames 16] [--reps 5] [--all]"""
 import argparse
 import ctypes as C
 import json
@@ -28,6 +28,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=16)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--all", action="store_true", help="time measure_cells plain and with every column family on, --reps calls "
+                    "each, instead of the numpy restatement")
     a = ap.parse_args()
     rng = np.random.Generator(np.random.PCG64(7))
     labels = stack(rng, a.frames)
@@ -82,6 +84,27 @@ def main():
     out["measure_cells_all_in_ms_per_frame"] = 1e3 * (time.perf_counter() - t0) / T
     print(f"  measure_cells all-in {out['measure_cells_all_in_ms_per_frame']:8.1f} ms per frame ({len(df)} rows; host floats and "
           "tracks included)")
+    if a.all:      # the host side: ``reps`` calls each after the warm-up above, plain and with every column family on
+        every = dict(drift=4, flow=2, flow_tile=64, gap=1, hull=True, midline=True, percentiles=(5, 50), neighbors=3,
+                     spots=1000, profile=4)
+        no_spots = {k: v for k, v in every.items() if k != "spots"}
+        for name, kw in (("plain", {}), ("all_but_spots", no_spots), ("all_on", every)):
+            try:
+                cells.measure_cells(lab_d, img_d, **kw)
+            except TypeError as e:      # drift and spots in one table: commits before the column families raise here
+                print(f"  measure_cells {name:13s} not timed: {type(e).__name__}: {e}")
+                continue
+            runs = []
+            for _ in range(a.reps):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                cells.measure_cells(lab_d, img_d, **kw)
+                runs.append(1e3 * (time.perf_counter() - t0) / T)
+            out[f"{name}_ms_per_frame_runs"] = [round(v, 3) for v in runs]
+            out[f"{name}_ms_per_frame_median"] = float(np.median(runs))
+            print(f"  measure_cells {name:13s} median {np.median(runs):8.2f} ms per frame, runs {min(runs):.2f} .. {max(runs):.2f}")
+        print(json.dumps(out))
+        return
     t0 = time.perf_counter()
     ref.table(labels[:2], img[:2], channels=list(range(Cn)), link=True)
     out["numpy_restatement_s_per_frame_per_core"] = (time.perf_counter() - t0) / 2
