@@ -9,7 +9,9 @@ their autograd backward (train.py:488).  Python only sequences kernels; every FL
 * the backward pass is explicit (dgrad / wgrad / norm-bwd kernels) and is exposed to PyTorch as ONE
   ``torch.autograd.Function`` so that ``loss.backward()`` and the stock optimizers keep working (plumbing only).
 """
+import collections
 import ctypes as C
+import functools
 import os
 
 import torch
@@ -189,94 +191,17 @@ def _dummy_pack(n, k):
     return (_round_up(n, 128), _round_up(k, 32))
 
 
-def bf16_storage_ok(spec, N, cin, H, W, training):
-    """Can this network run with bf16 tensor storage?  The bf16-storage forms exist for the bf16 matrix-core kernels, the
-    first-layer / head / normalisation kernels: every convolution launch of the forward pass (and, when a tape is kept, of
-    the backward pass) must map to one of them, channel counts must be multiples of 8 (16-byte staging loads of 8 bf16),
-    and the first layer must take the VALU kernels.  Otherwise bf16 mode keeps fp32 tensors (operand rounding only).
-    Whether a launch has a bf16 kernel is the LIBRARY's answer (mseg_igemm_query / mseg_wgrad_query on the descriptor the
-    launch would carry, with bf16 operands and destinations), not a rule restated here."""
-    if spec.pool_method == "max":
-        return False
-
-    def ig(cins, ngemm, nb, hi, wi, ho, wo, kh, kw, stride, pad, mode, epi=EPI_PLAIN, morder=MORDER_LINEAR, cq=0, taps=None):
-        npad, kpad = _dummy_pack(ngemm, sum(cins))
-        return igemm_query([_dummy_src(v) for v in cins], kpad, npad, nb, hi, wi, ho, wo, kh, kw, stride, pad, mode, ngemm,
-                           ld0=(cq if epi == EPI_SCATTER2X2 else ngemm), epi=epi, Cq=cq, morder=morder, precision="bf16",
-                           dst_dtype=ST_BF16) is not None
-
-    def wg(pc, qcs, nb, hp, wp, hq, wq, kh, kw, stride, pad):
-        return wgrad_query(_dummy_src(pc), [_dummy_src(v) for v in qcs], nb, hp, wp, hq, wq, kh, kw, stride, pad,
-                           precision="bf16") is not None
-
-    def conv_ok(cins, cout, hi, wi, stride):
-        ho, wo = (hi + 2 - 3) // stride + 1, (wi + 2 - 3) // stride + 1
-        c = sum(cins)
-        if any(v % 8 for v in cins) or cout % 8:
-            return False
-        if not ig(cins, cout, N, hi, wi, ho, wo, 3, 3, stride, 1, MODE_CONV):
-            return False
-        if training:
-            morder = MORDER_PARITY if stride == 2 else MORDER_LINEAR
-            if not ig([cout], c, N, ho, wo, hi, wi, 3, 3, stride, 1, MODE_TCONV, morder=morder):
-                return False
-            if not wg(cout, cins, N, ho, wo, hi, wi, 3, 3, stride, 1):
-                return False
-        return True
-
-    def up_ok(ci, co, hi, wi):
-        if ci % 8 or co % 8:
-            return False
-        if not ig([ci], 4 * co, N, hi, wi, hi, wi, 1, 1, 1, 0, MODE_CONV, epi=EPI_SCATTER2X2, cq=co):
-            return False
-        if training:
-            if not ig([co], ci, N, 2 * hi, 2 * wi, hi, wi, 2, 2, 2, 0, MODE_CONV):
-                return False
-            if not wg(ci, [co], N, hi, wi, 2 * hi, 2 * wi, 2, 2, 2, 0):
-                return False
-        return True
-
-    h, w = H, W
-    skips = []
-    c_prev = None
-    for i, e in enumerate(spec.enc):
-        c1o, c1i = e["c1"].conv.weight.shape[:2]
-        if i == 0:
-            if not _first_layer_ok(c1i, c1o, 1) or (training and c1i != 1) or c1o % 8:
-                return False
-        elif not conv_ok([c1i], c1o, h, w, 1):
-            return False
-        c2o = e["c2"].conv.weight.shape[0]
-        if not conv_ok([c1o], c2o, h, w, 1):
-            return False
-        c_prev = c2o
-        if e["pool"] is not None:
-            skips.append((c2o, h, w))
-            if not conv_ok([c2o], c2o, h, w, 2):
-                return False
-            h, w = (h + 2 - 3) // 2 + 1, (w + 2 - 3) // 2 + 1
-    for d in spec.decoders:
-        ch, hh, ww = c_prev, h, w
-        for lv, (cs, hs, wsk) in zip(d["levels"], reversed(skips)):
-            ci, co = lv["up"].conv.weight.shape[:2]
-            if ci != ch or not up_ok(ci, co, hh, ww):
-                return False
-            hh, ww = 2 * hh, 2 * ww
-            c1o = lv["c1"].conv.weight.shape[0]
-            if not conv_ok([co, cs], c1o, hh, ww, 1):
-                return False
-            c2o = lv["c2"].conv.weight.shape[0]
-            if not conv_ok([c1o], c2o, hh, ww, 1):
-                return False
-            ch = c2o
-        if ch % 8:
-            return False
-    return True
+# stand-ins for device tensors in a dispatch query: a storage type and an aligned address that nothing dereferences
+_PH = {ST_F32: torch.zeros(4, dtype=torch.float32), ST_BF16: torch.zeros(4, dtype=torch.bfloat16)}
 
 
 # ---- thin kernel wrappers ------------------------------------------------------------------------------------
 def _round_up(v, m):
     return (v + m - 1) // m * m
+
+
+def _pack_dims(T, R, Cc, st, sr, sc, merge_taps):      # (Npad, Kpad) of the GEMM operand of a pack_weight recipe
+    return _dummy_pack(T * R if merge_taps else R, Cc)
 
 
 _splitk_ws = {}      # (device, stream) -> grow-only scratch of the split-K igemm launches (stream-ordered reuse)
@@ -294,13 +219,12 @@ class PackedW:
     def __init__(self, param, T, R, Cc, st, sr, sc, merge_taps):
         self.param = param
         self.merge = merge_taps
-        self.Kpad = _round_up(Cc, 32)
+        self.Npad, self.Kpad = _pack_dims(T, R, Cc, st, sr, sc, merge_taps)
         if merge_taps:      # the T blocks of R rows back to back (one GEMM with N = T*R), padded as a whole
-            self.Npad = _round_up(T * R, 128)
             rpad = R
             self.t = torch.zeros(self.Npad * self.Kpad, dtype=torch.float32, device=param.device)
         else:
-            self.Npad = rpad = _round_up(R, 128)
+            rpad = self.Npad
             self.t = torch.empty(T * self.Npad * self.Kpad, dtype=torch.float32, device=param.device)
         self.job = (T, R, rpad, Cc, self.Kpad, st, sr, sc)
         self._t16 = None
@@ -432,23 +356,34 @@ def _query(fn, p):
     return KernelChoice(info) if rc == 0 else None
 
 
+def _igemm_desc(srcs, kpad, npad, bias, dst0, dst1, NB, Hi, Wi, Ho, Wo, KH, KW, stride, pad, mode, Ngemm, ld0, acc0=0, ld1=0,
+                acc1=0, split=None, epi=EPI_PLAIN, Cq=0, morder=MORDER_LINEAR):
+    """descriptor of a launch on tensors (or the _PH stand-ins: a question to the dispatch); weight and precision: the caller's"""
+    p = MsegIgemm()
+    _fill_igemm(p, srcs, kpad, npad, NB, Hi, Wi, Ho, Wo, KH, KW, stride, pad, mode, Ngemm, ld0, acc0, ld1, acc1, split, epi, Cq,
+                morder)
+    p.w = _DUMMY
+    p.dst_dtype = _st(dst0)                 # bf16 tensor storage: the C ABI accepts it for the bf16 kernels only
+    p.bias = _ptr(bias)
+    p.dst0 = dst0.data_ptr()
+    p.dst1 = _ptr(dst1)
+    return p
+
+
 def igemm_query(srcs, kpad, npad, NB, Hi, Wi, Ho, Wo, KH, KW, stride, pad, mode, Ngemm, ld0, acc0=0, ld1=0, acc1=0,
                 split=None, epi=EPI_PLAIN, Cq=0, morder=MORDER_LINEAR, precision=None, dst_dtype=ST_F32, bias=True):
     """mseg_igemm_query for a launch described by its shapes (placeholder pointers): the kernel the library would take, or
     None when it has none for this descriptor (e.g. precision 'bf16' on a shape without a bf16 kernel)."""
-    p = MsegIgemm()
-    _fill_igemm(p, srcs, kpad, npad, NB, Hi, Wi, Ho, Wo, KH, KW, stride, pad, mode, Ngemm, ld0, acc0, ld1, acc1, split, epi, Cq,
-                morder)
-    p.w = p.dst0 = _DUMMY
-    p.dst1 = _DUMMY if (split is not None and split < Ngemm) else None
-    p.bias = _DUMMY if bias else None
+    dst = _PH[dst_dtype]
+    p = _igemm_desc(srcs, kpad, npad, _PH[ST_F32] if bias else None, dst,
+                    dst if (split is not None and split < Ngemm) else None, NB, Hi, Wi, Ho, Wo, KH, KW, stride, pad, mode,
+                    Ngemm, ld0, acc0, ld1, acc1, split, epi, Cq, morder)
     p.precision = 1 if (precision or _precision) == "bf16" else 0
-    p.dst_dtype = dst_dtype
     return _query(_lib.load().mseg_igemm_query, p)
 
 
 _bf16_ok_cache = {}     # launch signature -> does the library have a bf16 kernel for it (toggles of the ablation hooks
-                        # switch between kernels of one precision, never the answer to this)
+                        # switch between kernels of one precision, never the answer to this); bf16_storage_ok asks it too
 
 
 def _igemm_bf16_ok(p):
@@ -482,14 +417,9 @@ def igemm(srcs, w, bias, NB, Hi, Wi, Ho, Wo, KH, KW, stride, pad, mode, Ngemm, d
     """`stats`: None, or (activation of the output, Workspace) — the caller would like the statistics of act(output) from
     this launch.  Returns None, or (partial-sum tensor, rows) when the kernel the library chose has taken them."""
     lib = _lib.load()
-    p = MsegIgemm()
-    _fill_igemm(p, srcs, w.Kpad, w.Npad, NB, Hi, Wi, Ho, Wo, KH, KW, stride, pad, mode, Ngemm, ld0, acc0, ld1, acc1, split, epi,
-                Cq, morder)
+    p = _igemm_desc(srcs, w.Kpad, w.Npad, bias, dst0, dst1, NB, Hi, Wi, Ho, Wo, KH, KW, stride, pad, mode, Ngemm, ld0, acc0,
+                    ld1, acc1, split, epi, Cq, morder)
     p.w = w.t.data_ptr()
-    p.dst_dtype = _st(dst0)                 # bf16 tensor storage: the C ABI accepts it for the bf16 kernels only
-    p.bias = _ptr(bias)
-    p.dst0 = dst0.data_ptr()
-    p.dst1 = _ptr(dst1)
     # bf16 mode: the launch runs on the bf16 matrix cores iff the library has a bf16 kernel for it (its dispatch, queried)
     bf16 = (precision or _precision) == "bf16" and _igemm_bf16_ok(p)
     if bf16:
@@ -599,19 +529,24 @@ def note_training_step():
     _stats_epoch += 1
 
 
+def _norm_form(node, norm):
+    """set the norm and the table stride (per channel | per sample and channel) -> is act(z) materialised for the consumers"""
+    node.norm = norm
+    node.ss = 0 if norm == NORM["bn"] else node.C
+    return node.act not in (ACT["none"], ACT["relu"])
+
+
 def norm_stats(node, norm, gamma, beta, running_mean, running_var, training, ws, conv_part=None):
     """Fill node.scale/shift (+mean/rstd) from a = act(z); BatchNorm eval mode uses the running statistics.
     `conv_part`: (partial sums, rows) left by the producing convolution's epilogue (training BatchNorm): the tensor is not
     read again."""
     lib = _lib.load()
     dev = node.z.device
-    node.norm = norm
     N, HW, Cc = node.N, node.H * node.W, node.C
-    expensive = node.act not in (ACT["none"], ACT["relu"])
+    expensive = _norm_form(node, norm)
     if expensive:
         node.a = torch.empty_like(node.z)
     if norm == NORM["bn"]:
-        node.ss = 0
         if not training:
             # eval-mode tables depend on the layer's parameters and running statistics only: computed once and kept on the
             # running_mean buffer until one of the four tensors changes (a frame of a stack re-used 34 tiny launches)
@@ -635,7 +570,6 @@ def norm_stats(node, norm, gamma, beta, running_mean, running_var, training, ws,
         node.mean = torch.empty(Cc, dtype=torch.float32, device=dev)
         node.rstd = torch.empty(Cc, dtype=torch.float32, device=dev)
     else:
-        node.ss = Cc
         node.scale = torch.empty(N * Cc, dtype=torch.float32, device=dev)
         node.shift = torch.empty(N * Cc, dtype=torch.float32, device=dev)
         ng = 8 if norm == NORM["gn"] else Cc
@@ -678,6 +612,8 @@ class ConvSpec:
     def __init__(self, kind, conv, norm_mod, act, norm):
         self.kind = kind            # 'conv' | 'pool' | 'up'
         self.conv = conv            # nn.Conv2d / nn.ConvTranspose2d (parameter holder)
+        a, b = conv.weight.shape[:2]                                    # ConvTranspose2d holds (in, out), Conv2d (out, in)
+        self.cin, self.cout = (a, b) if kind == "up" else (b, a)
         self.norm_mod = norm_mod    # nn.BatchNorm2d / nn.GroupNorm / nn.InstanceNorm2d
         self.act = ACT[act]
         self.norm = NORM[norm]
@@ -703,6 +639,7 @@ class NetSpec:
         self.enc = enc              # list of dict(c1=ConvSpec, c2=ConvSpec, pool=ConvSpec|None)
         self.decoders = decoders    # list (1 for U, 2 for DU) of dict(levels=[dict(up,c1,c2)], head=HeadSpec)
         self.pool_method = pool_method
+        self.bf16_storage = {}      # (N, cin, H, W, tape kept) -> bf16_storage_ok's answer (the layers' shapes are fixed)
 
     def layers(self):
         out = []
@@ -779,71 +716,101 @@ def normalize_frames(raw, pad_top=0, pad_left=0):
     return out
 
 
-def _first_layer_ok(cin, cout, stride):
-    return stride == 1 and 1 <= cin <= 4 and cout % 4 == 0 and cout <= 256 and 256 % (cout // 4) == 0
+FirstLayer = collections.namedtuple("FirstLayer", "fwd bwd bf16_storage")
 
 
-def _run_conv(spec, in_nodes, training, ws, tape, first_layer_cin=None, st=torch.float32):
-    """`st`: storage type of the layer's output z (torch.float32, or torch.bfloat16 in bf16-storage mode)"""
+def first_layer(cin, cout, raw=False, tape=False):
+    """The kernels of the network's first convolution (`raw`: the input is a RawFrame; `tape`: a backward pass follows).
+    fwd: 'raw' (mseg_first_conv_fwd_raw: normalisation and padding happen in the kernel's loads), 'valu' (mseg_first_conv_fwd:
+    9..36 MACs per output, an HBM-bound VALU kernel instead of a 32-channel MFMA K-step) or 'igemm' (input padded to 4 channels);
+    bwd: 'first_wgrad' (mseg_first_wgrad) or 'wgrad' (nch_store = cin); bf16_storage: only the VALU kernels store bf16."""
+    valu = 1 <= cin <= 4 and cout % 4 == 0 and cout <= 256 and 256 % (cout // 4) == 0
+    fused = raw and not tape and cin == 1 and cout % 8 == 0 and cout <= 256 and 256 % (cout // 8) == 0
+    fwd = "raw" if fused else "valu" if valu else "igemm"
+    bwd = "first_wgrad" if cin == 1 and valu else "wgrad"
+    return FirstLayer(fwd, bwd, valu and cout % 8 == 0 and (bwd == "first_wgrad" or not tape))
+
+
+# fwd / dgrad: keyword arguments of igemm(_query); wgrad: of wgrad(_query); pack_*: (T, R, Cc, st, sr, sc, merge_taps)
+LayerLaunches = collections.namedtuple("LayerLaunches", "out fwd dgrad wgrad dz_is_p pack_fwd pack_dgrad")
+
+
+@functools.lru_cache(maxsize=1024)
+def layer_launches(kind, cins, cout, N, Hi, Wi):
+    """The matrix launches of a layer, described ONCE for forward(), backward() and bf16_storage_ok(): forward, data gradient
+    and weight gradient of `kind` ('conv': 3x3 | 'pool': 3x3 stride 2 | 'up': ConvTranspose 2x2 stride 2) from sources of
+    `cins` channels (a tuple; two entries: a concat layer) to cout channels on N x Hi x Wi.  The answers are shared: read only."""
+    cin = sum(cins)
+    if kind == "up":
+        Ho, Wo = 2 * Hi, 2 * Wi
+        k = dict(KH=2, KW=2, stride=2, pad=0)
+        # y[2p+(a,b)][co] = sum_ci x[p][ci] W[ci][co][a][b]: ONE GEMM over the 4 taps, scattered by the epilogue
+        fwd = dict(NB=N, Hi=Hi, Wi=Wi, Ho=Hi, Wo=Wi, KH=1, KW=1, stride=1, pad=0, mode=MODE_CONV, Ngemm=4 * cout, ld0=cout,
+                   epi=EPI_SCATTER2X2, Cq=cout)
+        # dx[p][ci] = sum_{ab,co} dz[2p+(a,b)][co] W[ci][co][a][b]: a 2x2 stride-2 convolution of dz
+        dgrad = dict(NB=N, Hi=Ho, Wi=Wo, Ho=Hi, Wo=Wi, mode=MODE_CONV, Ngemm=cin, ld0=cin, **k)
+        # dW[ci][co][a][b] = sum x[p][ci] dz[2p+(a,b)][co]: P = the input, Q = dz
+        wgrad = dict(NB=N, Hp=Hi, Wp=Wi, Hq=Ho, Wq=Wo, **k)
+        return LayerLaunches((Ho, Wo), fwd, dgrad, wgrad, False, (4, cout, cin, 1, 4, cout * 4, True),
+                             (4, cin, cout, 1, cout * 4, 4, False))
+    stride = 2 if kind == "pool" else 1
+    Ho, Wo = (Hi + 2 - 3) // stride + 1, (Wi + 2 - 3) // stride + 1
+    k = dict(KH=3, KW=3, stride=stride, pad=1)
+    fwd = dict(NB=N, Hi=Hi, Wi=Wi, Ho=Ho, Wo=Wo, mode=MODE_CONV, Ngemm=cout, ld0=cout, **k)
+    # stride 2: rows in parity order; two inputs: the first one's columns go to its gradient, the rest to the second one's
+    dgrad = dict(NB=N, Hi=Ho, Wi=Wo, Ho=Hi, Wo=Wi, mode=MODE_TCONV, Ngemm=cin, ld0=cins[0],
+                 morder=MORDER_PARITY if stride == 2 else MORDER_LINEAR, **k)
+    if len(cins) == 2:
+        dgrad.update(split=cins[0], ld1=cins[1])
+    wgrad = dict(NB=N, Hp=Ho, Wp=Wo, Hq=Hi, Wq=Wi, **k)                  # P = dz, Q = the inputs
+    return LayerLaunches((Ho, Wo), fwd, dgrad, wgrad, True, (9, cout, cin, 1, cin * 9, 9, False),
+                         (9, cin, cout, 1, 9, cin * 9, False))
+
+
+def _wgrad_operands(L, dz, xs):
+    """(P, Qs) of the weight gradient from the source of dz and the sources of the layer's inputs"""
+    return (dz, xs) if L.dz_is_p else (xs[0], [dz])
+
+
+def _launches_of(spec, in_nodes, first):
+    """layer_launches of a layer on its input nodes (`first`: the network input, zero-padded to 4 channels)"""
+    n0, cins = in_nodes[0], tuple(n.C for n in in_nodes)
+    assert sum(cins) == (_pad4(spec.cin) if first else spec.cin), (spec.cin, cins)
+    return layer_launches(spec.kind, (spec.cin,) if first else cins, spec.cout, n0.N, n0.H, n0.W)
+
+
+def _run_conv(spec, in_nodes, training, ws, tape, first=False, st=torch.float32):
+    """`first`: the network's first convolution; `st`: storage type of the output z (torch.bfloat16 in bf16-storage mode)"""
     conv = spec.conv
     n0 = in_nodes[0]
-    N, Hi, Wi = n0.N, n0.H, n0.W
-    dev = n0.z.device
+    N, cin, cout = n0.N, spec.cin, spec.cout
+    L = _launches_of(spec, in_nodes, first)
+    Ho, Wo = L.out
     conv_part = None          # (partial sums, rows) when the convolution's epilogue has taken the BatchNorm statistics
-    if isinstance(n0.z, RawFrame):
-        srcs = []
-    cin_total = sum(n.C for n in in_nodes)
-    if not isinstance(n0.z, RawFrame):
-        srcs = [n.src() for n in in_nodes]
     bias = conv.bias.detach()
-    wt = conv.weight.detach()
-    if spec.kind == "up":
-        cin, cout = wt.shape[0], wt.shape[1]
-        assert cin == cin_total
-        wp = pack_weight(conv.weight, 4, cout, cin, 1, 4, cout * 4, merge_taps=True, kind="fwd")
-        Ho, Wo = 2 * Hi, 2 * Wi
-        z = torch.empty((N, Ho, Wo, cout), dtype=st, device=dev)
-        igemm(srcs, wp, bias, N, Hi, Wi, Hi, Wi, 1, 1, 1, 0, MODE_CONV, 4 * cout, z, cout,
-              epi=EPI_SCATTER2X2, Cq=cout)
-        act = ACT["none"]
+    z = torch.empty((N, Ho, Wo, cout), dtype=st, device=n0.z.device)
+    how = first_layer(cin, cout, isinstance(n0.z, RawFrame), tape is not None).fwd if first else "igemm"
+    if how == "raw":
+        check(_lib.load().mseg_first_conv_fwd_raw(*n0.z.args(), conv.weight.detach().contiguous().data_ptr(), bias.data_ptr(),
+                                                  cout, z.data_ptr(), _st(z), _stream()), "first_conv_fwd_raw")
+    elif how == "valu":
+        check(_lib.load().mseg_first_conv_fwd(n0.z.data_ptr(), conv.weight.detach().contiguous().data_ptr(), bias.data_ptr(),
+                                              N, n0.H, n0.W, cin, cout, z.data_ptr(), _st(z), _stream()), "first_conv_fwd")
     else:
-        cout, cin = wt.shape[0], wt.shape[1]
-        stride = 2 if spec.kind == "pool" else 1
-        if first_layer_cin is None:
-            assert cin == cin_total, (cin, cin_total)
-        else:
-            assert _pad4(cin) == cin_total, (cin, cin_total)   # network input is zero-padded to 4 channels
-        Ho, Wo = (Hi + 2 - 3) // stride + 1, (Wi + 2 - 3) // stride + 1
-        z = torch.empty((N, Ho, Wo, cout), dtype=st, device=dev)
-        if first_layer_cin is not None and isinstance(n0.z, RawFrame):
-            # inference on a raw frame: normalisation and padding happen in this kernel's loads
-            check(_lib.load().mseg_first_conv_fwd_raw(*n0.z.args(), wt.contiguous().data_ptr(), bias.data_ptr(), cout,
-                                                      z.data_ptr(), _st(z), _stream()), "first_conv_fwd_raw")
-        elif first_layer_cin is not None and _first_layer_ok(cin, cout, stride):
-            # raw network input, 9..36 MACs per output: HBM-bound VALU kernel instead of a 32-channel MFMA K-step
-            check(_lib.load().mseg_first_conv_fwd(n0.z.data_ptr(), wt.contiguous().data_ptr(), bias.data_ptr(), N, Hi,
-                                                  Wi, cin, cout, z.data_ptr(), _st(z), _stream()), "first_conv_fwd")
-        else:
-            wp = pack_weight(conv.weight, 9, cout, cin, 1, cin * 9, 9, kind="fwd")
-            want = (spec.act, ws) if (training and spec.norm == NORM["bn"] and
-                                      spec.act in (ACT["none"], ACT["relu"])) else None
-            conv_part = igemm(srcs, wp, bias, N, Hi, Wi, Ho, Wo, 3, 3, stride, 1, MODE_CONV, cout, z, cout, real_cin=cin,
-                              stats=want)
-        act = spec.act
+        wp = pack_weight(conv.weight, *L.pack_fwd, kind="fwd")
+        want = (spec.act, ws) if (spec.kind != "up" and training and spec.norm == NORM["bn"] and
+                                  spec.act in (ACT["none"], ACT["relu"])) else None
+        conv_part = igemm([n.src() for n in in_nodes], wp, bias, dst0=z, real_cin=cin, stats=want, **L.fwd)
     node = Node(z, N, Ho, Wo, cout)
-    node.act = act
+    node.act = ACT["none"] if spec.kind == "up" else spec.act
     node.layer = spec
     node.inputs = tuple(in_nodes)
     nm = spec.norm_mod
-    if spec.norm == NORM["bn"]:
-        norm_stats(node, spec.norm, nm.weight.detach(), nm.bias.detach(), nm.running_mean, nm.running_var,
-                   training, ws, conv_part=conv_part)
-        if training:
-            _nbt_pending.append(nm.num_batches_tracked)    # all layers' counters advance in ONE launch (end of forward)
-    elif spec.norm == NORM["gn"]:
-        norm_stats(node, spec.norm, nm.weight.detach(), nm.bias.detach(), None, None, training, ws)
-    else:
-        norm_stats(node, spec.norm, None, None, None, None, training, ws)
+    bn, affine = spec.norm == NORM["bn"], spec.norm in (NORM["bn"], NORM["gn"])
+    norm_stats(node, spec.norm, nm.weight.detach() if affine else None, nm.bias.detach() if affine else None,
+               nm.running_mean if bn else None, nm.running_var if bn else None, training, ws, conv_part=conv_part)
+    if bn and training:
+        _nbt_pending.append(nm.num_batches_tracked)    # all layers' counters advance in ONE launch (end of forward)
     if tape is not None:
         tape.nodes.append(node)
     return node
@@ -871,35 +838,102 @@ def _run_maxpool(src_node, tape):
 _nbt_pending = []      # BatchNorm num_batches_tracked tensors of the training forward in progress
 
 
+def _encode(spec, x, layer, maxpool=None):
+    """encoder on node x -> (bottom node, skip nodes); layer / maxpool: run one layer (forward) or ask about it (bf16_storage_ok)"""
+    skips = []
+    for i, e in enumerate(spec.enc):
+        x = layer(e["c1"], [x], first=i == 0)
+        x = layer(e["c2"], [x])
+        if e["pool"] is not None:
+            skips.append(x)
+            x = maxpool(x) if e["pool"] == "max" else layer(e["pool"], [x])
+    return x, skips
+
+
+def _decode(d, x, skips, layer):
+    """one decoder from the bottom node x up -> the node its head reads"""
+    for lv, skip in zip(d["levels"], reversed(skips)):
+        up = layer(lv["up"], [x])
+        x = layer(lv["c1"], [up, skip])
+        x = layer(lv["c2"], [x])
+    return x
+
+
+class _NoBf16Kernel(Exception):
+    pass
+
+
+def bf16_storage_ok(spec, N, cin, H, W, training):
+    """Can this network run with bf16 tensor storage?  Every convolution launch of the forward pass (and, when a tape is
+    kept, of the backward pass) must have a bf16 matrix-core kernel, channel counts must be multiples of 8 (16-byte staging
+    loads of 8 bf16), the first layer must take the VALU kernels; otherwise bf16 mode keeps fp32 tensors (operand rounding
+    only).  Nothing about a launch is restated here: forward()'s own _encode / _decode walk the network on stand-in nodes,
+    each launch is the one layer_launches() describes, and whether it has a bf16 kernel is the LIBRARY's answer to the cached
+    question the launches themselves ask (destinations as first contributions, acc 0).  The answer is kept on the NetSpec."""
+    key = (N, cin, H, W, bool(training))
+    if key not in spec.bf16_storage:
+        spec.bf16_storage[key] = _all_launches_bf16(spec, N, cin, H, W, training)
+    return spec.bf16_storage[key]
+
+
+def _all_launches_bf16(spec, N, cin, H, W, training):
+    if spec.pool_method == "max":       # _run_maxpool stores fp32
+        return False
+    t16, t32 = _PH[ST_BF16], _PH[ST_F32]
+
+    def igemm_ok(srcs, pack, bias, geo):
+        npad, kpad = _pack_dims(*pack)
+        return _igemm_bf16_ok(_igemm_desc(srcs, kpad, npad, bias, t16, t16 if "split" in geo else None, **geo))
+
+    def wgrad_ok(P, Qs, geo):
+        p = MsegWgrad()
+        _fill_wgrad(p, P, Qs, nch_store=None, **geo)
+        return _wgrad_bf16_ok(p)
+
+    def layer(sp, ins, first=False):
+        L = _launches_of(sp, ins, first)
+        if first:
+            ok = first_layer(sp.cin, sp.cout, tape=training).bf16_storage
+        else:
+            xs, dz = [n.src() for n in ins], plain_src(t16, sp.cout)
+            ok = not (sp.cout % 8 or any(n.C % 8 for n in ins)) and igemm_ok(xs, L.pack_fwd, t32, L.fwd)
+            if ok and training:
+                ok = igemm_ok([dz], L.pack_dgrad, None, L.dgrad) and wgrad_ok(*_wgrad_operands(L, dz, xs), L.wgrad)
+        if not ok:
+            raise _NoBf16Kernel
+        node = Node(t16, N, L.out[0], L.out[1], sp.cout)
+        node.act = ACT["none"] if sp.kind == "up" else sp.act
+        node.a = t16 if _norm_form(node, sp.norm) else None
+        node.scale = node.shift = t32
+        return node
+
+    try:
+        bottom, skips = _encode(spec, Node(t32, N, H, W, _pad4(cin)), layer)
+        for d in spec.decoders:
+            _decode(d, bottom, skips, layer)
+    except _NoBf16Kernel:
+        return False
+    return True
+
+
 def forward(spec, x, training, keep_tape, ws):
     """x: (N, ch_in, H, W) fp32 CUDA tensor.  Returns (list of NCHW outputs, Tape|None)."""
     lib = _lib.load()
     del _nbt_pending[:]
     raw = x if isinstance(x, RawFrame) else None
-    if raw is not None:
-        # a raw frame (inference): fused into the first convolution when that layer takes the row-walking VALU kernel,
-        # else normalised into an fp32 tensor by one streaming kernel
-        c1 = spec.enc[0]["c1"].conv.weight
-        fused = (not keep_tape and c1.shape[1] == 1 and c1.shape[0] % 8 == 0 and c1.shape[0] <= 256 and
-                 256 % (c1.shape[0] // 8) == 0)
-        if not fused:
-            x, raw = raw.normalized(), None
-    if raw is not None:
-        N, cin, H, W = 1, 1, raw.H, raw.W
-    else:
-        N, cin, H, W = x.shape
-    nlev = len(spec.enc)
-    div = 2 ** (nlev - 1)
+    c1 = spec.enc[0]["c1"]
+    if raw is not None and first_layer(c1.cin, c1.cout, raw=True, tape=keep_tape).fwd != "raw":
+        x, raw = raw.normalized(), None       # no fused first kernel: normalised into an fp32 tensor by one streaming kernel
+    N, cin, H, W = (1, 1, raw.H, raw.W) if raw is not None else x.shape
+    div = 2 ** (len(spec.enc) - 1)
     if H % div or W % div:
         raise RuntimeError(f"input {H}x{W} is not divisible by {div}")
     dev = x.device
-    c4 = _pad4(cin)
-    if raw is not None:
-        xin = Node(raw, N, H, W, c4)
-    else:
-        x4 = torch.zeros((N, H, W, c4), dtype=torch.float32, device=dev)
+    x4 = raw
+    if raw is None:
+        x4 = torch.zeros((N, H, W, _pad4(cin)), dtype=torch.float32, device=dev)
         x4[..., :cin] = x.detach().permute(0, 2, 3, 1)
-        xin = Node(x4, N, H, W, c4)
+    xin = Node(x4, N, H, W, _pad4(cin))
     tape = Tape() if keep_tape else None
     if tape is not None:
         tape.x4 = xin
@@ -907,18 +941,10 @@ def forward(spec, x, training, keep_tape, ws):
     st = torch.bfloat16 if (_precision == "bf16" and _bf16_storage and
                             bf16_storage_ok(spec, N, cin, H, W, keep_tape)) else torch.float32
 
-    cur = xin
-    skips = []
-    for i, e in enumerate(spec.enc):
-        cur = _run_conv(e["c1"], [cur], training, ws, tape, first_layer_cin=cin if i == 0 else None, st=st)
-        cur = _run_conv(e["c2"], [cur], training, ws, tape, st=st)
-        if e["pool"] is not None:
-            skips.append(cur)
-            if e["pool"] == "max":
-                cur = _run_maxpool(cur, tape)
-            else:
-                cur = _run_conv(e["pool"], [cur], training, ws, tape, st=st)
-    bottom = cur
+    def layer(ws_):
+        return lambda sp, ins, first=False: _run_conv(sp, ins, training, ws_, tape, first, st)
+
+    bottom, skips = _encode(spec, xin, layer(ws), lambda node: _run_maxpool(node, tape))
     outs = []
     # The decoders of a DU-Net are independent of each other: in bf16 mode the second one runs on its own stream, so that the
     # HBM-bound statistics passes and the store bursts of one decoder lie under the matrix kernels of the other.  Its tensors
@@ -931,11 +957,7 @@ def forward(spec, x, training, keep_tape, ws):
         main = torch.cuda.current_stream(dev)
 
     def run_decoder(d, ws_):
-        cur = bottom
-        for lv, skip in zip(d["levels"], reversed(skips)):
-            up = _run_conv(lv["up"], [cur], training, ws_, tape, st=st)
-            cur = _run_conv(lv["c1"], [up, skip], training, ws_, tape, st=st)
-            cur = _run_conv(lv["c2"], [cur], training, ws_, tape, st=st)
+        cur = _decode(d, bottom, skips, layer(ws_))
         hc = d["head"].conv
         co = hc.weight.shape[0]
         out = torch.empty((N, co, H, W), dtype=torch.float32, device=dev)
@@ -963,7 +985,7 @@ def forward(spec, x, training, keep_tape, ws):
 
 
 # ---- backward --------------------------------------------------------------------------------------------------
-def _accumulate_target(node, shape_like):
+def _accumulate_target(node):
     """Return (tensor, acc_flag) for writing a gradient contribution into node.grad."""
     if node.grad is None:
         node.grad = torch.empty_like(node.z)
@@ -1114,7 +1136,7 @@ def backward(spec, tape, grad_outs, ws, on_grads=None, direct=None):
             raise RuntimeError("internal: node without gradient")
         if sp is _MaxPoolMarker:
             i0 = node.inputs[0]
-            tgt, acc = _accumulate_target(i0, None)
+            tgt, acc = _accumulate_target(i0)
             s = i0.src()
             check(lib.mseg_maxpool2x2_bwd(C.byref(s), i0.N, i0.H, i0.W, gy.data_ptr(), tgt.data_ptr(), acc, _stream()),
                   "maxpool_bwd")
@@ -1130,47 +1152,26 @@ def backward(spec, tape, grad_outs, ws, on_grads=None, direct=None):
             grads[id(nm.weight)] = dgamma
             grads[id(nm.bias)] = dbeta
         grads[id(conv.bias)] = dbias
-        wt = conv.weight.detach()
         dW = _grad_buf(conv.weight, direct)
         ins = node.inputs
         i0 = ins[0]
-        N = node.N
-        if sp.kind == "up":
-            cin, cout = wt.shape[0], wt.shape[1]
-            # dW[ci][co][a][b] = sum x[p][ci] * dz[2p+(a,b)][co]
-            on_side(dz, lambda w_, i0=i0, dz=dz, dW=dW, cout=cout, node=node: wgrad(
-                i0.src(), [plain_src(dz, cout)], dW, N, i0.H, i0.W, node.H, node.W, 2, 2, 2, 0, w_))
-            # dx[p][ci] = sum_{ab,co} dz[2p+(a,b)][co] * W[ci][co][a][b]
-            wp = pack_weight(conv.weight, 4, cin, cout, 1, cout * 4, 4, kind="dgrad")
-            tgt, acc = _accumulate_target(i0, None)
-            igemm([plain_src(dz, cout)], wp, None, N, node.H, node.W, i0.H, i0.W, 2, 2, 2, 0, MODE_CONV, cin,
-                  tgt, cin, acc0=acc)
+        N, cout = node.N, sp.cout
+        is_first = i0 is tape.x4
+        cin, L = sp.cin, _launches_of(sp, ins, is_first)
+        if is_first and first_layer(cin, cout, tape=True).bwd == "first_wgrad":
+            w1 = ws.get("first_wgrad", lib.mseg_first_wgrad_workspace_bytes(N, node.H, node.W, cout))
+            check(lib.mseg_first_wgrad(i0.z.data_ptr(), dz.data_ptr(), _st(dz), N, node.H, node.W, cout, dW.data_ptr(),
+                                       w1.data_ptr(), _stream()), "first_wgrad")
         else:
-            cout, cin = wt.shape[0], wt.shape[1]
-            stride = 2 if sp.kind == "pool" else 1
-            is_first = i0 is tape.x4
-            if is_first and cin == 1 and _first_layer_ok(cin, cout, stride):
-                w1 = ws.get("first_wgrad", lib.mseg_first_wgrad_workspace_bytes(N, node.H, node.W, cout))
-                check(lib.mseg_first_wgrad(i0.z.data_ptr(), dz.data_ptr(), _st(dz), N, node.H, node.W, cout, dW.data_ptr(),
-                                           w1.data_ptr(), _stream()), "first_wgrad")
-            else:
-                on_side(dz, lambda w_, dz=dz, ins=ins, dW=dW, cout=cout, node=node, i0=i0, stride=stride, cin=cin,
-                        is_first=is_first: wgrad(plain_src(dz, cout), [n.src() for n in ins], dW, N, node.H, node.W, i0.H,
-                                                 i0.W, 3, 3, stride, 1, w_, nch_store=cin if is_first else None))
-            if not is_first:
-                wp = pack_weight(conv.weight, 9, cin, cout, 1, 9, cin * 9, kind="dgrad")
-                morder = MORDER_PARITY if stride == 2 else MORDER_LINEAR
-                if len(ins) == 1:
-                    tgt, acc = _accumulate_target(i0, None)
-                    igemm([plain_src(dz, cout)], wp, None, N, node.H, node.W, i0.H, i0.W, 3, 3, stride, 1,
-                          MODE_TCONV, cin, tgt, cin, acc0=acc, morder=morder)
-                else:
-                    i1 = ins[1]
-                    t0, a0 = _accumulate_target(i0, None)
-                    t1, a1 = _accumulate_target(i1, None)
-                    igemm([plain_src(dz, cout)], wp, None, N, node.H, node.W, i0.H, i0.W, 3, 3, stride, 1,
-                          MODE_TCONV, cin, t0, i0.C, acc0=a0, dst1=t1, ld1=i1.C, acc1=a1,
-                          split=i0.C, morder=morder)
+            def weight_grad(w_, dz=dz, ins=ins, dW=dW, cout=cout, L=L, nst=cin if is_first else None):
+                P, Qs = _wgrad_operands(L, plain_src(dz, cout), [n.src() for n in ins])
+                wgrad(P, Qs, dW, ws=w_, nch_store=nst, **L.wgrad)
+            on_side(dz, weight_grad)
+        if not is_first:
+            wp = pack_weight(conv.weight, *L.pack_dgrad, kind="dgrad")
+            tgt, acc = _accumulate_target(i0)
+            t1, a1 = _accumulate_target(ins[1]) if len(ins) == 2 else (None, 0)
+            igemm([plain_src(dz, cout)], wp, None, dst0=tgt, acc0=acc, dst1=t1, acc1=a1, **L.dgrad)
         grads[id(conv.weight)] = dW
         if on_grads is not None:        # data-parallel: gradients of this layer are final -> start their all-reduce
             on_grads([dW, dbias, dgamma, dbeta])

@@ -84,6 +84,20 @@ def bf16_rule(kind, xs, ws):
             wg(cout, cin, H, W, H, W, 3, 1, 1))
 
 
+def storage_grid():
+    """tests/golden/bf16_storage_grid.json: engine.bf16_storage_ok's answers, recorded before the launches were described in
+    one place -> ({name: dict(unet, filters, ch_in, pool)}, {(name, N, H, training): answer}); H = W"""
+    import json
+    with open(GOLDEN / "bf16_storage_grid.json") as f:
+        g = json.load(f)
+    table = {}
+    for name, cfg in g["networks"].items():
+        keys = [(name, n, h, tr) for n in g["N"] for h in g["H"] for tr in g["training"]]
+        assert len(keys) == len(cfg["answers"])
+        table.update(zip(keys, (c == "1" for c in cfg["answers"])))
+    return g["networks"], table
+
+
 class NodeTrace:
     """records every engine Node of a forward pass (execution order) by wrapping engine.norm_stats"""
 

@@ -484,6 +484,40 @@ def test_bf16_mode_matches_bf16_oracle(ut, act, norm, filters, size, batch, dev)
         assert _l2_rel(p.grad.cpu(), p16[k].grad) < max(3e-2, 1.5 * noise), k
 
 
+@pytest.mark.parametrize("batch,size", [(2, 48), (3, 48), (2, 64)])
+@pytest.mark.parametrize("name,ut,norm,filters,ch_in,pool", [("DU_64_128", "DU", "bn", (64, 128), 1, "conv"),
+                                                             ("DU_64_128_in3", "DU", "bn", (64, 128), 3, "conv"),
+                                                             ("DU_64_128_max", "DU", "bn", (64, 128), 1, "max"),
+                                                             ("U_8_16", "U", "gn", (8, 16), 1, "conv")])
+def test_bf16_storage_decision_is_what_the_passes_do(name, ut, norm, filters, ch_in, pool, batch, size, dev):
+    """engine.bf16_storage_ok against the passes it decides for, on shapes that straddle the decision (DU (64, 128): bf16
+    tensors when training at 2 x 48 x 48, fp32 at 3 x 48 x 48; ch_in = 3: bf16 for eval only): every tensor of a training
+    forward + backward and of an eval forward is stored as the decision says, the decision is the recorded one
+    (tests/golden/bf16_storage_grid.json), and the passes complete — the dispatch answers MSEG_EINVAL for a bf16 tensor on a
+    launch without a bf16 kernel — with finite outputs and parameter gradients."""
+    from helpers import storage_grid
+    from microbeseg_amd import engine
+    from microbeseg_amd.utils.unets import build_unet
+    table = storage_grid()[1]
+    torch.manual_seed(7)
+    net = build_unet(ut, "relu", pool, norm, dev, 1, ch_in=ch_in, ch_out=3 if ut == "U" else 1, filters=filters)
+    x = (torch.rand(batch, ch_in, size, size) * 2 - 1).to(dev)
+    with engine.precision_scope("bf16"):
+        for training in (True, False):
+            want = engine.bf16_storage_ok(net._spec, batch, ch_in, size, size, training)
+            assert want == table[(name, batch, size, training)], (name, batch, size, training)
+            net.train(training)
+            with NodeTrace() as tr, torch.set_grad_enabled(training):
+                outs = net(x)
+                outs = outs if isinstance(outs, tuple) else (outs,)
+                if training:
+                    torch.autograd.backward(outs, [torch.ones_like(o) for o in outs])
+            assert tr.nodes and all((n.z.dtype == torch.bfloat16) == want for n in tr.nodes), (training, want)
+            assert all(torch.isfinite(o).all() for o in outs)
+            if training:
+                assert all(p.grad is not None and torch.isfinite(p.grad).all() for p in net.parameters())
+
+
 @pytest.mark.parametrize("optimizer", ["fused_adam", "torch_capturable"])
 @pytest.mark.parametrize("precision", ["fp32", "bf16"])
 def test_graphed_train_step_equals_eager(precision, optimizer, dev, request):
